@@ -17,6 +17,9 @@ Prints ONE JSON line (rank 0).  `value` = spots/s of the whole job = steps/s x g
 call timed with HIP events on its launch stream in an eager pass right after the timed region (same process, same
 resident model and inputs; every kernel alone on the GPU: side streams off).  `cpu_baseline` = the CPU oracle
 (oracle/ref_cpu.py) timed on this host's cores on the same workload, a bounded number of steps (N=1 only).
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``).  The inputs and the
+model's initial state are seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -73,7 +76,15 @@ def parse():
                          "rocprofv3 traces under profiles/ record; results are bit-identical to the two-lane step")
     ap.add_argument("--launch_check", action="store_true",
                     help="only exercise the launcher + process group (works without a GPU, gloo): prints a JSON line")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", dest="dump_outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (loss, embeddings, parameters, "
+                         "gradients, BatchNorm statistics) as DIR/<name>.npy (rank 0; see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def _host_cores() -> int:
@@ -256,6 +267,51 @@ def kernel_roofline(step_fn, n_steps: int, model) -> list:
     return rows
 
 
+# ------------------------------------------------------------------------------------------------ output dump
+DUMP_SAMPLE = 32768            # elements kept per tensor: all of a smaller one, a fixed seeded sample of a larger one
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def _dump_sample(t):
+    """fp32 host copy of ``t`` flattened; above DUMP_SAMPLE elements only the positions drawn by a generator seeded with 0
+    (sorted), so two runs -- or two builds -- sample the same elements of a tensor of the same size."""
+    import numpy as np
+    f = t.detach().reshape(-1)
+    if f.numel() > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(0).choice(f.numel(), DUMP_SAMPLE, replace=False))
+        f = f[torch.from_numpy(idx).to(f.device)]
+    return f.float().cpu().numpy()
+
+
+def dump_outputs(out_dir: str, loss, trainer, model) -> dict:
+    """What the timed path hands its caller after its last step, as ``out_dir/<name>.npy``:
+      loss                       float64 (1,)
+      spot_embedding, image_embedding   fp32 (B, 256) of the last step (graph replay only: the captured output buffers)
+      param.<name>, grad.<name>, buffer.<name>   fp32, flattened (sampled above DUMP_SAMPLE elements): the parameters the
+                                 step's optimizer update left (position tables materialised), their gradients of the last
+                                 step, the BatchNorm running statistics
+    Called outside the timed region, before anything else runs a step."""
+    import numpy as np
+    arrays = {"loss": np.array([float(loss)], dtype=np.float64)}
+    if trainer.graphs and trainer.es is not None and trainer.ei is not None:
+        arrays["spot_embedding"] = trainer.es.detach().float().cpu().numpy()
+        arrays["image_embedding"] = trainer.ei.detach().float().cpu().numpy()
+    for n, p in model.named_parameters():
+        arrays["param." + n] = _dump_sample(p)
+        if p.grad is not None:
+            arrays["grad." + n] = _dump_sample(p.grad)
+    for n, b in model.named_buffers():
+        if b.is_floating_point():
+            arrays["buffer." + n] = _dump_sample(b)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "arrays": len(arrays), "bytes": total}
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 def launch_check() -> None:
     """Launcher / rendezvous self-test (no GPU needed): every rank contributes rank+1 to an all-reduce."""
@@ -366,6 +422,7 @@ def main():
     dt = time.perf_counter() - t0
     log(f"host enqueue {1e3 * t_host:.2f} ms/step (first {n_host} steps), wall {1e3 * dt / args.steps:.2f} ms/step "
         f"({'HOST-bound' if t_host > 0.9 * dt / args.steps else 'GPU-bound'})")
+    final_loss_t = loss.detach()
     final_loss = float(loss.item())
     if dist_on:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -390,6 +447,11 @@ def main():
                        "amortized_ms_per_step": round(mat_ms / max(1, behind), 5),
                        "note": "NOT inside the timed region: a checkpoint (model.state_dict()) pays full_materialize_ms once; "
                                "ms_per_step + amortized_ms_per_step is the all-inclusive figure"}
+
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, final_loss_t, trainer, model)
+        log(f"outputs of the last timed step: {dumped['arrays']} arrays, {dumped['bytes']} bytes under {dumped['dir']}")
 
     # per-kernel roofline: eager pass with HIP events around the hot C-ABI calls (rank 0's GPU; N = 1 only, so that the
     # collectives of the other ranks are not left waiting)
@@ -456,6 +518,8 @@ def main():
                 "note": "sum over the listed launch units of their strict algorithmic bytes per step / the TIMED step (graph "
                         "replay, lanes overlapped) / 8 TB/s; 2.21 TFLOP per step (SURVEY section 8d)"} if roof_rows else None),
         }
+        if dumped is not None:
+            out["outputs_dump"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             log("gpu done: %.2f ms/step; timing the CPU oracle baseline" % out["ms_per_step"])
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_budget_s)

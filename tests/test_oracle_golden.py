@@ -11,6 +11,20 @@ from oracle import ref_cpu
 from helpers import (GOLDEN_CASES, UNTOUCHED_ROW, assert_close, assert_close_scaled, layer_sample, load_golden,
                      oracle_forward, sample)
 
+# torch's CPU reductions and MKL's GEMM split their fp32 sums by thread count, and the tolerances below are a few fp32
+# ulps of the compared values.  With 8 intra-op threads the oracle reproduces the fixtures within them; with 1 or 4 it
+# rounds differently by more than that.  Pinned, the outcome does not depend on the host's core count.  (A CPU on which
+# MKL picks other GEMM kernels, such as an AMD EPYC, rounds differently at any thread count.)
+FIXTURE_THREADS = 8
+
+
+@pytest.fixture(autouse=True)
+def _fixture_thread_count():
+    n = torch.get_num_threads()
+    torch.set_num_threads(FIXTURE_THREADS)
+    yield
+    torch.set_num_threads(n)
+
 
 @pytest.mark.parametrize("name", GOLDEN_CASES)
 def test_oracle_matches_reference_fixture(name):
