@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCL_ABI_VERSION 9
+#define MCL_ABI_VERSION 10
 
 #define MCL_OK 0
 #define MCL_EINVAL (-1)       /* null pointer / non-positive size / inconsistent arguments */
@@ -781,6 +781,31 @@ int mcl_knn_weighted_average(const float* spot_key, int64_t ldk, const float* ex
                              const float* query, int64_t ldq, const int64_t* indices, int32_t n_query, int32_t k,
                              int32_t dim, int32_t genes, int32_t ord, float* emb_pred, float* expr_pred,
                              mcl_stream_t stream);
+
+/* ---------------------------------------------------------------- scoring of expression predictions
+ * Replaces, on the device, the closing block of the reference's evaluation scripts for ALL folds at once:
+ *   evel_her2st.py:196-226, evel_cscc.py:226-261, evel_visium.py:212-244 and utils.py:52-65 (get_R, dim=1).
+ * pred, truth: rows x G, leading dimensions ld_pred / ld_true (elements), dtype codes 0 = fp32, 1 = fp64, each its own.
+ * offsets: S + 1 int64 row offsets IN DEVICE MEMORY, one segment (fold) per pair; preconditions the caller checks (the
+ *   library cannot read them before launching): offsets[0] >= 0, strictly increasing, every segment >= 2 rows
+ *   (scipy.stats.pearsonr raises below 2), offsets[S] <= the rows of both matrices.  Inputs are finite.
+ * Per segment s, all fp64 (row-major, gene g at [s * G + g]):
+ *   r[S x G]          Pearson r of pred[:, g] against truth[:, g] over the segment (scipy.stats.pearsonr as get_R calls it):
+ *                     NaN when either column is exactly constant over the segment, otherwise clipped to [-1, 1];
+ *   true_mean[S x G]  mean of truth[:, g] over the segment;
+ *   heg[S x n_heg]    int64: the n_heg genes with the largest true_mean, best first, equal means by ascending gene index
+ *                     (np.argsort(mean)[::-1][:50], evel_her2st.py:201-202);
+ *   summary[S x 5]    { heg_pcc = mean of r over heg (NaN propagates, np.mean), hvg_pcc = mean of r over the non-NaN genes
+ *                     (evel_her2st.py:209-213; NaN if there are none), mse = mean over genes of the per-gene mean of
+ *                     (truth - pred)^2, mae = the same with |truth - pred| (sklearn's uniform average over outputs),
+ *                     n_valid = the number of non-NaN r };
+ *   work              2 * S * G doubles of scratch (the per-gene errors).
+ * fp64 accumulation in two passes (means, then centred sums); no atomics: the reduction order depends only on
+ * (segment length, G, n_heg), so a segment scored inside a batch is bit-identical to the same segment scored alone.
+ * 1 <= n_heg <= G; S <= 65535.                                                                                    */
+int mcl_expr_metrics(const void* pred, int64_t ld_pred, int32_t pred_dtype, const void* truth, int64_t ld_true,
+                     int32_t true_dtype, const int64_t* offsets, int32_t S, int32_t G, int32_t n_heg, double* r,
+                     double* true_mean, int64_t* heg, double* summary, double* work, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;

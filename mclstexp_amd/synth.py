@@ -143,3 +143,27 @@ def make_retrieval_case(n_keys: int, n_query: int, dim: int = 256, genes: int = 
         key[n_keys - duplicates:] = key[0]
     return {"spot_key": np.ascontiguousarray(key), "image_query": np.ascontiguousarray(qry.astype(np.float32)),
             "expression_key": np.ascontiguousarray(expr)}
+
+
+def make_eval_case(segments: Sequence[int], genes: int, seed: int = 0, const_true: Sequence[int] = (),
+                   const_pred: Sequence[int] = (), heg_const: bool = False) -> Dict[str, np.ndarray]:
+    """Synthetic scoring problem for ``mclstexp_amd.evaluate``: folds of ``segments[i]`` spots stacked row-wise.
+    ``true`` (rows, genes) is log-normalised expression (~60 % zeros, a per-gene scale so the gene means spread out);
+    ``pred`` (rows, genes) is 0.5 * true + uniform noise, like a k-NN average of expression rows.  Both float64 (the
+    reference's prediction buffers are ``np.zeros`` float64).  Columns in ``const_true`` / ``const_pred`` are constant
+    (Pearson r undefined -> NaN); ``heg_const`` makes the last gene a constant column with the largest true mean (so
+    it is one of the highest-expressed genes).  ``offsets`` (len(segments) + 1,) int64 are the fold boundaries."""
+    rows = int(sum(segments))
+    u = uniform_tensor("eval.true", (rows, genes), 0.0, 1.0, seed).numpy().astype(np.float64)
+    scale = 0.2 + 3.0 * uniform_tensor("eval.gene_scale", (genes,), 0.0, 1.0, seed).numpy().astype(np.float64)
+    true = np.where(u < 0.6, 0.0, (u - 0.6) * 10.0) * scale[None, :]
+    noise = uniform_tensor("eval.pred_noise", (rows, genes), 0.0, 2.0, seed).numpy().astype(np.float64)
+    pred = 0.5 * true + noise
+    for g in const_true:
+        true[:, g] = 1.5
+    for g in const_pred:
+        pred[:, g] = 0.75
+    if heg_const:
+        true[:, genes - 1] = 2.0 * float(true.mean(axis=0).max()) + 1.0
+    offsets = np.concatenate([[0], np.cumsum(np.asarray(segments, dtype=np.int64))]).astype(np.int64)
+    return {"pred": np.ascontiguousarray(pred), "true": np.ascontiguousarray(true), "offsets": offsets}
