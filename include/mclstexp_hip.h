@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCL_ABI_VERSION 10
+#define MCL_ABI_VERSION 11
 
 #define MCL_OK 0
 #define MCL_EINVAL (-1)       /* null pointer / non-positive size / inconsistent arguments */
@@ -82,9 +82,8 @@ typedef struct mcl_gemm_args {
    * candidate list: pos = atomic flt_cnt[i]++ (zero on entry), flt_val[i * flt_cap + pos] = value, flt_idx[...] = j when
    * pos < flt_cap (flt_cnt keeps counting past the capacity: the caller sees the overflow).  batch 1, no split-K, no epilogue. */
   const float* flt_thr; int32_t* flt_cnt; float* flt_val; int32_t* flt_idx; int32_t flt_cap;
-  /* ABI 9: split-K in ONE launch.  counters != NULL (and ksplit > 1, 64x64 tiles): ceil(M/64) * ceil(N/64) * batch uint32, ZERO on
-   * entry and left zero -- the last K slice to arrive at a tile adds the slices in slice order and applies the epilogue itself
-   * (bit-identical to the two-launch form); one counter array per concurrently running call (e.g. per stream).  NULL: two launches. */
+  /* Reserved (ABI 9 - 10: split-K in one launch, measured slower and removed at ABI 11).  Ignored: split-K always merges the
+   * slices in a second launch, and the array, if any, is neither read nor written. */
   uint32_t* counters;
 } mcl_gemm_args;
 
@@ -280,7 +279,13 @@ int mcl_cast_f32_to_bf16(const float* x, int64_t ldx, void* y, int64_t ldy, int6
  * attention products.  bias [N] fp32, resid [M][N] bf16 (outer-batch stride sRb, 0 = broadcast).  Leading dimensions multiples of 8 (bf16) /
  * 4 (fp32 C); ragged M, N, K allowed; bf16 C needs ldc >= round_up(N, 8).  ksplit > 1 (fp32 output, batch 1, no
  * epilogue): the K range is split over workgroups, fp32 slabs in `workspace` (mcl_gemm_bf16_workspace_floats) are
- * merged in fixed order into C (accumulate != 0: +=) -- the weight-gradient form, deterministic.                      */
+ * merged in fixed order into C (accumulate != 0: +=) -- the weight-gradient form, deterministic.
+ * ABI 11: flags bits 7-8 choose among the kernels that apply to the problem (for tests and A/B runs; production passes 0):
+ * 0 auto (the pipelined kernel for bf16 output, the staggered one for fp32), 1 the lockstep kernel only, 2 the lockstep or
+ * the staggered kernel, never the pipelined one, 3 the pipelined kernel wherever it applies (fp32 output included).  A
+ * value never forces a kernel onto a problem it does not apply to (the staggered kernel: interior 256 x 256 tiles only; the
+ * pipelined one: also K ranges of >= 128).  The lockstep and staggered kernels agree bit for bit, the pipelined one too
+ * except for one bf16 ulp on the GELU epilogues.                                                                         */
 int64_t mcl_gemm_bf16_workspace_floats(int32_t M, int64_t ldc, int32_t ksplit);
 int mcl_gemm_bf16(const void* A, int64_t lda, int64_t sAb, const void* B, int64_t ldb, int64_t sBb, void* C, int64_t ldc,
                   int64_t sCb, int32_t M, int32_t N, int32_t K, int32_t batch, int32_t batch2, int64_t sAb2, int64_t sBb2,

@@ -17,7 +17,7 @@ import torch  # noqa: F401  (side effect: loads torch/lib/libamdhip64.so)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCL_LIB_PATH") or os.path.join(_HERE, "libmclstexp_hip.so")   # override: A/B of kernel builds
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 _lib: Optional[C.CDLL] = None
 
@@ -44,7 +44,7 @@ class GemmArgs(C.Structure):
         ("compute", c_i), ("ksplit", c_i),
         ("workspace", c_p),
         ("flt_thr", c_p), ("flt_cnt", c_p), ("flt_val", c_p), ("flt_idx", c_p), ("flt_cap", c_i),
-        ("counters", c_p),
+        ("counters", c_p),                # reserved since ABI 11: ignored by the library
     ]
 
 

@@ -42,7 +42,6 @@ struct mcl_device_once {
     return guard{this, bit, !(done.load(std::memory_order_acquire) & bit)};
   }
 };
-// environment overrides of grid sizes: never below 1 (atoi of garbage / "0" / a negative value would launch a zero-size grid)
 // compute units of the current device (cached per device id; 256 on MI355X): the grid of persistent kernels
 static inline int mcl_cu_count() {
   static int cached[64];
@@ -55,12 +54,6 @@ static inline int mcl_cu_count() {
     cached[d] = n;
   }
   return cached[d];
-}
-
-static inline int mcl_env_grid(const char* value, int dflt) {
-  if (!value) return dflt;
-  const int v = atoi(value);
-  return v < 1 ? 1 : v;
 }
 
 __device__ __forceinline__ float wave_sum(float v) {

@@ -266,11 +266,10 @@ int mcl_launch_conv3x3_wrw_rows(const void* dy, long long lddy, const void* z, l
   const WrwRowsPlan p = wrw_rows_plan(S, H, W);
   const size_t ring_bytes = (size_t)WR_NWAVE * ((size_t)16 * p.nks * 64 + 3 * (size_t)(16 * p.nks + 2) * 64);
   const size_t lds_bytes = ring_bytes > (size_t)WR_RED_BYTES ? ring_bytes : (size_t)WR_RED_BYTES;
-  static bool attr_done = false;
-  if (!attr_done) {
+  static mcl_device_once attr_once;
+  if (auto attr_guard = attr_once.first()) {
     (void)hipFuncSetAttribute((const void*)conv3x3_wrw_rows_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     (void)hipFuncSetAttribute((const void*)conv3x3_wrw_rows_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_done = true;
   }
   if (p.nks == 2)
     hipLaunchKernelGGL((conv3x3_wrw_rows_kernel<2>), dim3(p.grid), dim3(64 * WR_NWAVE), lds_bytes, st, (const bf16_t*)dy, lddy,
@@ -279,5 +278,6 @@ int mcl_launch_conv3x3_wrw_rows(const void* dy, long long lddy, const void* z, l
     hipLaunchKernelGGL((conv3x3_wrw_rows_kernel<4>), dim3(p.grid), dim3(64 * WR_NWAVE), lds_bytes, st, (const bf16_t*)dy, lddy,
                        (const bf16_t*)z, p.nimg, H, W, gamma, beta, mean, rstd, p.rc, p.nchunk, workspace);
   mcl_launch_wrw_merge(workspace, p.grid, (long long)WR_MN, dW, accumulate_w, st);
+  MCL_CHECK_LAUNCH();
   return MCL_OK;
 }

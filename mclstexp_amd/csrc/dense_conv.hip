@@ -17,7 +17,6 @@
 // stored as whole 256-byte rows.  Statistics: per-tile (sum, M2) about a per-tile shift, merged by a one-wave-per
 // -channel finalize with Chan's formula in double (deterministic, no atomics).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -867,10 +866,7 @@ extern "C" int mcl_dense_conv3x3_wrw_det(const void* dy, int64_t lddy, const voi
   const int ntile = (int)((S + T3 - 1) / T3);
   hipStream_t st = mcl_stream(stream);
   if (mcl_conv3x3_wrw_rows_applicable(S, H, W)) {
-    const int rc = mcl_launch_conv3x3_wrw_rows(dy, lddy, z, S, H, W, gamma, beta, mean, rstd, workspace, dW, accumulate_w, st);
-    if (rc != MCL_OK) return rc;
-    MCL_CHECK_LAUNCH();
-    return MCL_OK;
+    return mcl_launch_conv3x3_wrw_rows(dy, lddy, z, S, H, W, gamma, beta, mean, rstd, workspace, dW, accumulate_w, st);
   }
   // per pixel group ONE fp32 partial (32 x 1152) in the workspace, written in disjoint column ranges by its three kernel-row
   // workgroups; fixed-order merge launch (bit-reproducible)
@@ -1080,7 +1076,7 @@ __global__ __launch_bounds__(256, 3) void conv0_fwd_kernel(const bf16_t* __restr
 // The workgroup's fp32 partial (64 x 7 x 21) goes to its workspace slot (fixed-order merge launch: deterministic).
 __global__ __launch_bounds__(256, 2) void conv0_wrw_kernel(const bf16_t* __restrict__ x, int N, int H, int W,
                                                            const bf16_t* __restrict__ dy, float* __restrict__ dW,
-                                                           int ntile, float* __restrict__ wpart, int dbg) {
+                                                           int ntile, float* __restrict__ wpart) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int OH = H >> 1, OW = W >> 1;
   const int PW = (W + 6) * 3 + 8;
@@ -1148,7 +1144,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wrw_kernel(const bf16_t* __restr
 #pragma unroll
     for (int u = 0; u < NDY; ++u) {
       const int c = tid + 256 * u;
-      if (c < npix * 8 && !(dbg & 1)) {
+      if (c < npix * 8) {
         const int px = c >> 3, c8 = c & 7;
         const int pc = px < OW ? px : px - OW + OWp;            // row in the padded [2][OWp] pixel layout
         *reinterpret_cast<u32x4*>(dyt + pc * 128 + ((c8 ^ (((pc >> 1) & 1) << 2)) << 4)) = rdy[u];
@@ -1157,7 +1153,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wrw_kernel(const bf16_t* __restr
 #pragma unroll
     for (int u = 0; u < NX; ++u) {
       const int c = tid + 256 * u;
-      if (c < 9 * cpr && !(dbg & 2)) {
+      if (c < 9 * cpr) {
         const int r = c / cpr, cc = c % cpr;
         bf16_t* d = slab + r * PW + 9 + cc * 8;          // odd element offset: 2-byte stores
         const bool ok = (xvalid >> u) & 1u;              // (a row outside the image: zeros)
@@ -1171,7 +1167,7 @@ __global__ __launch_bounds__(256, 2) void conv0_wrw_kernel(const bf16_t* __restr
     }
     __syncthreads();
 
-    for (int p0 = 0; p0 < 2 * OWp && !(dbg & 4); p0 += 16) {           // k-step: (padded) pixels p0 .. p0 + 15 of one output row
+    for (int p0 = 0; p0 < 2 * OWp; p0 += 16) {           // k-step: (padded) pixels p0 .. p0 + 15 of one output row
       const int rr = p0 / OWp, ox0 = p0 - rr * OWp;
       const unsigned char* ap = dyt + (p0 + 8 * h) * 128 + a_off;
       const v4s alo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)(ap));
@@ -1276,10 +1272,8 @@ extern "C" int mcl_conv0_wrw(const void* x, int32_t N, int32_t H, int32_t W, con
   }
   hipStream_t st = mcl_stream(stream);
   const int grid = conv0_wrw_grid(ntile);
-  // timing ablations for tools/bench_stem.py (results invalid): 1 no dy tile, 2 no input slab, 4 no MFMA loop
-  static const int dbg = getenv("MCL_CONV0_WRW_DBG") ? atoi(getenv("MCL_CONV0_WRW_DBG")) : 0;
   hipLaunchKernelGGL(conv0_wrw_kernel, dim3(grid), dim3(256), lds_bytes, st, (const bf16_t*)x, N, H, W,
-                     (const bf16_t*)dy, dW, ntile, workspace, dbg);
+                     (const bf16_t*)dy, dW, ntile, workspace);
   mcl_launch_wrw_merge(workspace, grid, (long long)C0_OUT * C0_K * 21, dW, accumulate_w, st);
   MCL_CHECK_LAUNCH();
   return MCL_OK;

@@ -28,7 +28,6 @@
 // gemm_bf16_stag_kernel -- same tile, same fragments, same k order (bit-identical results), but the two wave groups run one
 // barrier apart over a four-slot half-K ring filled three ahead: +6...19 % on the ViT shapes (below).
 #include "common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -109,7 +108,6 @@ struct GemmB {
   int gelu, gelu_bwd, out_f32;
   int tm, tn, ksplit;                           // tiles in M, N; K slices (slab s at C + s * slab_stride floats)
   long long k_per_split, slab_stride;
-  int dbg;                                      // experiment switches of the pipe kernel (MCL_GEMM_DBG; 0 in production)
 };
 
 // GELU (exact-erf form, nn.GELU's default) and its derivative for bf16 outputs.  Phi(x) = 0.5 erfc(-x / sqrt 2) through Abramowitz &
@@ -647,7 +645,7 @@ __device__ __forceinline__ void pipe_epilogue(const GemmB& g, f32x16 (&acc)[4][2
     for (int t = 0; t < 4; ++t) {
       const int r = (lane >> 3) + 8 * t, c = lane & 7;
       const u32x4 v = *reinterpret_cast<const u32x4*>(stage + r * 128 + ((c ^ (r & 7)) << 4));
-      if (!(g.dbg & 1) || v[0] == 0x12345678u) *reinterpret_cast<u32x4*>(rowbase + (long long)r * ld + c * 8) = v;
+      *reinterpret_cast<u32x4*>(rowbase + (long long)r * ld + c * 8) = v;
     }
   };
   bf16_t* cblk = reinterpret_cast<bf16_t*>(g.C) + cur.c_off + (long long)mw * g.ldc + nw;
@@ -765,7 +763,7 @@ __device__ __forceinline__ void pipe_epilogue(const GemmB& g, f32x16 (&acc)[4][2
 // the workgroups started half a tile apart, at one workgroup per CU, and with the tile's stores trickled out one per half-tile
 // of the next tile from parked registers (profiles/r06_gemm_pipe_experiments.txt); the code path stays generic, only WN = 4 is
 // instantiated.
-template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int WN, int DBG = 0>
+template <bool A_KMAJOR, bool B_KMAJOR, int EPI, int WN>
 __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, int total_virtual) {
   constexpr int NW = 2 * WN;                      // waves
   constexpr int BM = 256, BN = 64 * WN;
@@ -864,14 +862,12 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, in
   auto dma_part = [&](int part) {
     if (!pf_active) return;
     const unsigned d = lds_base + spf * SLOT + wave_s * 1024;
-    if (!(DBG & 8)) {
 #pragma unroll
-      for (int e = 0; e < PPS; ++e) glds16s(pfA, vA[part][e], d + part * HSUB + e * NW * 1024);
-      if (WN == 4) {
-        glds16s(pfB, vB[part % BSUBS][0], d + HOP + (part % BSUBS) * HSUB);
-      } else {
-        glds16s(pfB, vB[0][part % PPS], d + HOP + (part % PPS) * NW * 1024);
-      }
+    for (int e = 0; e < PPS; ++e) glds16s(pfA, vA[part][e], d + part * HSUB + e * NW * 1024);
+    if (WN == 4) {
+      glds16s(pfB, vB[part % BSUBS][0], d + HOP + (part % BSUBS) * HSUB);
+    } else {
+      glds16s(pfB, vB[0][part % PPS], d + HOP + (part % PPS) * NW * 1024);
     }
     if (part == 1) {
       spf = spf + 1 == NSLOT ? 0 : spf + 1;
@@ -903,9 +899,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, in
     return frag_km(tB, 16 * q + 8 * h, cb + j * 32, lane);
   };
 #define MCL_SB() __builtin_amdgcn_sched_barrier(0)
-#define MCL_MFMA(I, J, FA, FB) \
-  do { if (!(DBG & 4)) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FB[J], FA[I], acc[I][J], 0, 0, 0); \
-       else acc[I][J][0] += __builtin_bit_cast(float, FA[I][0] ^ FB[J][0]); } while (0)
+#define MCL_MFMA(I, J, FA, FB) acc[I][J] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(FB[J], FA[I], acc[I][J], 0, 0, 0)
   // counted waits on the vector-memory counter (immediates): n = instructions that may stay in flight
   auto wait_vm = [&](int n) {
     switch (n) {
@@ -964,7 +958,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, in
       else if (!first_tile && x < D - 1) wait_vm(VM_STEADY + S);
       else wait_vm(VM_STEADY);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (!(DBG & 16)) __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_s_barrier();
       // ---- k-step 1: MFMAs on (fa1, fb1) | reads of k-step 0 of the NEXT half-tile (the next tile's first one at a tile end)
       MCL_SB();
       MCL_MFMA(0, 0, fa1, fb1); fb0[0] = read_b(s1, 0, 0); MCL_SB();
@@ -980,7 +974,7 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, in
       sc = s1;
     }
 
-    if (!(g.dbg & 2)) pipe_epilogue<EPI, WN>(g, acc, cur, wm, wn, h, l31, lds + NSLOT * SLOT + wave * 4096);
+    pipe_epilogue<EPI, WN>(g, acc, cur, wm, wn, h, l31, lds + NSLOT * SLOT + wave * 4096);
     if (!nxt_valid) break;
     cur = nxt;
     nxt_valid = false;
@@ -1001,7 +995,8 @@ __global__ __launch_bounds__(128 * WN, 2) void gemm_bf16_pipe_kernel(GemmB g, in
 
 // flags: bit 0 A reduction-major, bit 1 B reduction-major, bit 2 GELU, bit 3 multiply by gelu'(aux), bit 4 fp32 output,
 // bit 5 (with bit 2 and pre_out): pre_out receives gelu'(pre-activation) instead of the pre-activation, bit 6: multiply by aux itself
-// (aux = that stored derivative): the backward's epilogue then needs no exp / rcp per element
+// (aux = that stored derivative): the backward's epilogue then needs no exp / rcp per element, bits 7-8: kernel choice (see
+// include/mclstexp_hip.h)
 extern "C" int64_t mcl_gemm_bf16_workspace_floats(int32_t M, int64_t ldc, int32_t ksplit) {
   if (M <= 0 || ldc <= 0 || ksplit <= 1) return 0;
   return (int64_t)ksplit * ((int64_t)M * ldc + 64);
@@ -1037,7 +1032,6 @@ extern "C" int mcl_gemm_bf16(const void* A, int64_t lda, int64_t sAb, const void
   g.resid = (const bf16_t*)resid; g.ldr = ldr; g.sRb = sRb;
   g.aux = (const bf16_t*)aux; g.ldaux = ldaux;
   g.pre_out = (bf16_t*)pre_out; g.ldp = ldp;
-  g.dbg = 0;
   g.gelu = gelu ? (gelu_grad_out ? 2 : 1) : 0; g.gelu_bwd = gbwd ? (aux_is_grad ? 2 : 1) : 0; g.out_f32 = f32;
   // small problems (batched attention products) take the 128 x 128 tile, two workgroups per CU
   const int subs = (M <= 512 && N <= 512) ? 1 : 2;
@@ -1070,20 +1064,18 @@ extern "C" int mcl_gemm_bf16(const void* A, int64_t lda, int64_t sAb, const void
     MCL_ATTR_S(false, false); MCL_ATTR_S(false, true); MCL_ATTR_S(true, false); MCL_ATTR_S(true, true);
 #undef MCL_ATTR_S
   }
-  // the staggered kernel where every tile is interior (MCL_GEMM_STAG=0: the lockstep kernel; bit-identical results; read per
-  // launch -- tests flip it inside one process)
-  const char* e_stag = getenv("MCL_GEMM_STAG");
-  const bool stag = subs == 2 && !(e_stag && e_stag[0] == '0') && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && kps % 64 == 0 &&
+  // kernel choice (flags bits 7-8, for tests and A/B runs): 0 auto, 1 the lockstep kernel only, 2 never the pipelined kernel,
+  // 3 the pipelined kernel wherever it applies.  The staggered kernel where every tile is interior (bit-identical results):
+  const int kernel_sel = (flags >> 7) & 3;
+  const bool stag = subs == 2 && kernel_sel != 1 && M % 256 == 0 && N % 256 == 0 && K % 64 == 0 && kps % 64 == 0 &&
                     lda * 512 < (1ll << 31) && ldb * 512 < (1ll << 31);
-  // the persistent pipelined kernel (round 6) wherever the staggered one applies and every K range holds >= 4 half-tiles.
-  // MCL_GEMM_PIPE (read per launch -- tests and A/B runs flip it inside one process): "0" never, anything else always, unset =
-  // where it measured faster than the staggered kernel (profiles/r06_gemm_pipe_experiments.txt 8): every bf16-output epilogue
+  // the persistent pipelined kernel (round 6) wherever the staggered one applies and every K range holds >= 4 half-tiles; by
+  // default where it measured faster than the staggered kernel (profiles/r06_gemm_pipe_experiments.txt 8): every bf16-output epilogue
   // (qkv / fc1 / fc2 -1 ... -3 %, the gelu'-multiplying data gradient -19 %); the fp32 split-K slabs of the weight gradients stay
   // on the staggered kernel (+9 % there).
-  const char* e_pipe = getenv("MCL_GEMM_PIPE");
   const long long last_range = (long long)K - (long long)(g.ksplit - 1) * kps;
   const bool pipe_ok = stag && last_range >= 128 && kps >= 128 && !(gbwd && resid) && !(gelu && (gbwd || resid));
-  const bool pipe = pipe_ok && (e_pipe ? e_pipe[0] != '0' : !f32);
+  const bool pipe = pipe_ok && (kernel_sel == 0 ? !f32 : kernel_sel == 3);
   if (pipe) {
     const int total_virtual = per_batch * batch;
     const int cus = mcl_cu_count();
@@ -1091,8 +1083,6 @@ extern "C" int mcl_gemm_bf16(const void* A, int64_t lda, int64_t sAb, const void
     const int G = total_virtual < slots ? total_virtual : slots;
     const int epi = f32 ? PE_F32 : gelu ? (gelu_grad_out ? PE_GELU2 : PE_GELU1) : gbwd ? (aux_is_grad ? PE_GBWD2 : PE_GBWD1)
                     : resid ? PE_RESID : PE_PLAIN;
-    const char* e_dbg = getenv("MCL_GEMM_DBG");           // experiment switches: 1 no stores, 2 no epilogue, 4 / 8 / 16 loop ablations
-    g.dbg = e_dbg ? atoi(e_dbg) : 0;
     const int lay = (akm ? 2 : 0) | (bkm ? 1 : 0);
     using KernelT = void (*)(GemmB, int);
 #define MCL_PK(AK, BKM) {gemm_bf16_pipe_kernel<AK, BKM, PE_PLAIN, 4>, gemm_bf16_pipe_kernel<AK, BKM, PE_GELU2, 4>,   \
@@ -1101,24 +1091,14 @@ extern "C" int mcl_gemm_bf16(const void* A, int64_t lda, int64_t sAb, const void
                          gemm_bf16_pipe_kernel<AK, BKM, PE_F32, 4>}
     static const KernelT table[4][7] = {MCL_PK(false, false), MCL_PK(false, true), MCL_PK(true, false), MCL_PK(true, true)};
 #undef MCL_PK
-    static const KernelT dbg_table[4] = {gemm_bf16_pipe_kernel<false, false, PE_PLAIN, 4, 4>, gemm_bf16_pipe_kernel<false, false, PE_PLAIN, 4, 8>,
-                                         gemm_bf16_pipe_kernel<false, false, PE_PLAIN, 4, 12>, gemm_bf16_pipe_kernel<false, false, PE_PLAIN, 4, 16>};
     static mcl_device_once pipe_once;
     if (auto guard = pipe_once.first()) {
       for (int a = 0; a < 4; ++a)
         for (int e = 0; e < 7; ++e)
           (void)hipFuncSetAttribute(reinterpret_cast<const void*>(table[a][e]), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 32768);
-      for (int e = 0; e < 4; ++e)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dbg_table[e]), hipFuncAttributeMaxDynamicSharedMemorySize, 5 * 32768);
-    }
-    KernelT kern = table[lay][epi];
-    if (g.dbg & 28) {                                     // loop ablations (NT, plain): 4 no MFMA, 8 no DMA, 16 no barrier
-      if (lay != 0 || epi != PE_PLAIN) return MCL_EUNSUPPORTED;
-      const int d = g.dbg & 28;
-      kern = d == 4 ? dbg_table[0] : d == 8 ? dbg_table[1] : d == 12 ? dbg_table[2] : dbg_table[3];
     }
     // LDS: the four-slot ring (128 KB) + 4 KB of epilogue staging per wave = all 160 KB of the CU
-    hipLaunchKernelGGL(kern, dim3(G), dim3(512), (size_t)(5 * 32768), st, g, total_virtual);
+    hipLaunchKernelGGL(table[lay][epi], dim3(G), dim3(512), (size_t)(5 * 32768), st, g, total_virtual);
     if (via_slabs) {
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return (int)e;

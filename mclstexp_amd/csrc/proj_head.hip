@@ -526,11 +526,10 @@ extern "C" int mcl_proj_head_fwd(const float* x, int64_t ldx, int32_t M, int32_t
   const int nrb = (M + RB - 1) / RB;
   const bool vec = al16(x) && al16(wp) && al16(wf) && ldx % 4 == 0 && ldwp % 4 == 0 && ldwf % 4 == 0 && D % 4 == 0;
   const size_t lds = FWD_LDS_FLOATS * sizeof(float);
-  static bool once = false;
-  if (!once) {
+  static mcl_device_once attr_once;
+  if (auto attr_guard = attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proj_head_fwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proj_head_fwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    once = true;
   }
   hipStream_t st = mcl_stream(stream);
   if (vec) hipLaunchKernelGGL(proj_head_fwd_kernel<true>, dim3(h.ks, nrb), dim3(NT), lds, st, h);
@@ -554,10 +553,9 @@ extern "C" int mcl_proj_head_bwd_rows(const float* de, int64_t ldde, int32_t M, 
   h.accumulate = accumulate_mask; h.ws = ws; h.cnt = counter;
   h.nrb = (M + RB - 1) / RB;
   const size_t lds = BWD_LDS_FLOATS * sizeof(float);
-  static bool once = false;
-  if (!once) {
+  static mcl_device_once attr_once;
+  if (auto attr_guard = attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(proj_head_bwd_rows_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    once = true;
   }
   hipLaunchKernelGGL(proj_head_bwd_rows_kernel, dim3(h.nrb), dim3(NT), lds, mcl_stream(stream), h);
   MCL_CHECK_LAUNCH();

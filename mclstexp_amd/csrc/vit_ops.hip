@@ -545,8 +545,8 @@ int launch_patchify(const float* img, int64_t sb, int64_t sc, int64_t sy, int64_
     if (blocks8 > 65535 * 4) blocks8 = 65535 * 4;
     hipLaunchKernelGGL(patchify8_kernel, dim3((unsigned)blocks8), dim3(256), 0, mcl_stream(stream), img, (long long)sb,
                        (long long)sc, (long long)sy, B, H, W, p, lead, (bf16_t*)out);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? MCL_OK : (int)e;
+    MCL_CHECK_LAUNCH();
+    return MCL_OK;
   }
   long long blocks = (total + 255) / 256;
   if (blocks > 65535 * 4) blocks = 65535 * 4;
@@ -556,8 +556,8 @@ int launch_patchify(const float* img, int64_t sb, int64_t sc, int64_t sy, int64_
   else
     hipLaunchKernelGGL(patchify_kernel<bf16_t>, dim3((unsigned)blocks), dim3(256), 0, mcl_stream(stream), img, (long long)sb,
                        (long long)sc, (long long)sy, (long long)sx, B, H, W, p, lead, (bf16_t*)out);
-  hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MCL_OK : (int)e;
+  MCL_CHECK_LAUNCH();
+  return MCL_OK;
 }
 }  // namespace
 

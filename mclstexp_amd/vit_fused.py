@@ -28,6 +28,9 @@ Tensor = torch.Tensor
 BF = torch.bfloat16
 A_KM, B_KM, GELU, GELU_BWD, OUT_F32 = 1, 2, 4, 8, 16
 GELU_GRAD_OUT, AUX_IS_GRAD = 32, 64           # fc1 stores gelu'(pre-activation); the data gradient multiplies by it directly
+# kernel choice (flags bits 7-8; production passes none: tests compare the kernels): lockstep only, never the pipelined kernel,
+# the pipelined kernel wherever it applies
+KERNEL_LOCKSTEP, KERNEL_NO_PIPE, KERNEL_PIPE = 1 << 7, 2 << 7, 3 << 7
 
 
 def _st() -> int:

@@ -156,3 +156,28 @@ def test_gemm_args_struct_size_is_honoured():
     g = _lib.gemm_args()
     assert g.struct_size == C.sizeof(full)
     assert fn(C.byref(g), None) == -1                                   # sized, but null operands
+
+
+def _nm_tool():
+    """llvm-nm of the ROCm toolchain that builds the library (next to hipcc), else binutils' nm."""
+    import shutil
+    hipcc = shutil.which("hipcc")
+    if hipcc:
+        cand = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "llvm", "bin", "llvm-nm")
+        if os.path.exists(cand):
+            return cand
+    return shutil.which("llvm-nm") or shutil.which("nm")
+
+
+def test_library_reads_no_environment():
+    """Kernel choice and experiment switches travel through arguments: the shipped library imports no getenv."""
+    import subprocess
+    from mclstexp_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build(verbose=False)
+    nm = _nm_tool()
+    assert nm, "no nm / llvm-nm to read the library's symbols"
+    out = subprocess.run([nm, "-D", "--undefined-only", _lib.LIB_PATH], capture_output=True, text=True, check=True).stdout
+    undefined = {line.split()[-1].split("@")[0] for line in out.splitlines() if line.strip()}
+    assert "memcpy" in undefined                     # (the listing was read)
+    assert not undefined & {"getenv", "secure_getenv"}, sorted(undefined & {"getenv", "secure_getenv"})

@@ -1,5 +1,6 @@
 """Per-kernel parity: each C-ABI entry point (through ops.py) against the CPU oracle / fp64 torch on
 the same seeded inputs.  Run on the MI355X box:  pytest -m gpu."""
+import ctypes
 import math
 
 import numpy as np
@@ -97,37 +98,56 @@ def test_gemm_splitk_matches_one_pass_and_is_deterministic(ops):
 
 @pytest.mark.parametrize("M,N,K,batch", [(128, 1536, 1000, 1), (128, 256, 1024, 1), (33, 171, 785, 1), (40, 70, 500, 3), (128, 1000, 512, 1)])
 def test_gemm_splitk_one_launch_equals_two_launches(ops, M, N, K, batch):
-    """The last-arriver merge inside the product's launch == partials + a second launch, bit for bit (same slice order), with
-    every epilogue; repeated calls find the arrival counters clean."""
+    """ABI 11: the one-launch split-K is gone and mcl_gemm_args.counters is reserved -- a split-K call that passes an
+    arrival-counter array (what selected the one-launch form at ABI 9 - 10; that layout:
+    ceil(M / 64) * ceil(N / 64) * batch uint32, zero) equals the call without one bit for bit, with every epilogue, and leaves
+    the array untouched."""
     from mclstexp_amd import _lib
-    assert _lib.lib().mcl_gemm_auto_ksplit(M, N, K, batch) > 1
+    L = _lib.lib()
+    ks = L.mcl_gemm_auto_ksplit(M, N, K, batch)
+    assert ks > 1
     A, B = _rand(batch, M, K, seed=1).to(DEV), _rand(batch, K, N, seed=2, scale=1 / math.sqrt(K)).to(DEV)
     bias, resid, aux = _rand(N, seed=3).to(DEV), _rand(M, N, seed=4).to(DEV), _rand(M, N, seed=5).to(DEV)
+    counters = torch.zeros(((M + 63) // 64) * ((N + 63) // 64) * batch, device=DEV, dtype=torch.int32)
 
-    def run(one, **kw):
-        ops.SPLIT_K_ONE_LAUNCH = one
-        try:
-            Cm = torch.full((batch, M, N), 0.5, device=DEV)
-            pre = torch.empty(M, N, device=DEV) if kw.pop("pre", False) else None
-            ops.gemm_raw(M, N, K, batch, A, K, 1, M * K, B, N, 1, K * N, Cm, N, M * N, pre_out=pre, ldp=N if pre is not None else 0,
-                         **kw)
-            torch.cuda.synchronize()
-            return Cm, pre
-        finally:
-            ops.SPLIT_K_ONE_LAUNCH = False
+    def run(with_counters, flags=0, alpha=1.0, bias=None, resid=None, ldr=0, aux=None, ldaux=0, pre=False):
+        Cm = torch.full((batch, M, N), 0.5, device=DEV)
+        pre_out = torch.empty(M, N, device=DEV) if pre else None
+        if not with_counters:      # the production path
+            ops.gemm_raw(M, N, K, batch, A, K, 1, M * K, B, N, 1, K * N, Cm, N, M * N, alpha=alpha, flags=flags, bias=bias,
+                         resid=resid, ldr=ldr, aux=aux, ldaux=ldaux, pre_out=pre_out, ldp=N if pre else 0)
+        else:
+            ws = torch.empty(ks * batch * M * N, device=DEV)
+            a = _lib.gemm_args()
+            a.M, a.N, a.K, a.batch = M, N, K, batch
+            a.A, a.sAm, a.sAk, a.sAb = A.data_ptr(), K, 1, M * K
+            a.B, a.sBk, a.sBn, a.sBb = B.data_ptr(), N, 1, K * N
+            a.C, a.ldc, a.sCb = Cm.data_ptr(), N, M * N
+            a.alpha, a.flags = alpha, flags
+            a.bias = None if bias is None else bias.data_ptr()
+            a.resid, a.ldr, a.sRb = (None if resid is None else resid.data_ptr()), ldr, 0
+            a.pre_out, a.ldp = (None if pre_out is None else pre_out.data_ptr()), N if pre else 0
+            a.aux, a.ldaux = (None if aux is None else aux.data_ptr()), ldaux
+            a.compute = ops._compute_mode
+            a.ksplit, a.workspace = ks, ws.data_ptr()
+            a.counters = counters.data_ptr()
+            _lib.check(L.mcl_gemm(ctypes.byref(a), torch.cuda.current_stream().cuda_stream), "mcl_gemm")
+        torch.cuda.synchronize()
+        return Cm, pre_out
 
     cases = [dict(), dict(flags=_lib.EPI_ACCUM, alpha=0.5)]
     if batch == 1:
         cases += [dict(flags=_lib.EPI_GELU, bias=bias, resid=resid, ldr=N, pre=True),
                   dict(flags=_lib.EPI_GELU_BWD, aux=aux, ldaux=N, resid=resid, ldr=N)]
     for kw in cases:
-        two = run(False, **dict(kw))
+        ref = run(False, **kw)
         for _ in range(3):
-            one = run(True, **dict(kw))
-            assert torch.equal(one[0], two[0]), kw
-            if two[1] is not None:
-                assert torch.equal(one[1], two[1]), kw
-    assert_close_scaled(run(True)[0].cpu(), A.cpu().double() @ B.cpu().double(), 2e-6, what="one-launch split-K")
+            got = run(True, **kw)
+            assert torch.equal(got[0], ref[0]), kw
+            if ref[1] is not None:
+                assert torch.equal(got[1], ref[1]), kw
+            assert not counters.any(), kw
+    assert_close_scaled(run(True)[0].cpu(), A.cpu().double() @ B.cpu().double(), 2e-6, what="split-K with counters")
 
 
 def test_linear_bwd_weight_accumulates_into_param_grad(ops):

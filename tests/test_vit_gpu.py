@@ -45,9 +45,9 @@ def test_gemm_bf16_layouts(M, N, K, akm, bkm):
     # several tiles per persistent workgroup (576 / 1152 tiles on 256 / 512 workgroups), the ViT block's own epilogue forms
     (16384, 2304, 768, 0, 0, "bias_gelu2"), (16384, 2304, 256, 0, 1, "gelu_bwd2"), (16384, 2304, 384, 0, 0, "resid"),
     (16384, 2304, 128, 1, 0, "bias"), (2304, 768, 16384, 1, 1, "f32_splitk")])
-def test_gemm_bf16_staggered_kernel_bit_identical(M, N, K, akm, bkm, mode, monkeypatch):
+def test_gemm_bf16_staggered_kernel_bit_identical(M, N, K, akm, bkm, mode):
     """gemm_bf16_stag_kernel (problems of interior 256 x 256 tiles: two wave groups one barrier apart over a four-slot half-K
-    ring) against the lockstep kernel (MCL_GEMM_STAG=0): same fragments in the same k order and the same epilogue, so equal
+    ring) against the lockstep kernel (vf.KERNEL_LOCKSTEP): same fragments in the same k order and the same epilogue, so equal
     bit for bit -- all four operand layouts, 1 / 2 / 3 / many half-tiles (shorter than, equal to and longer than the ring),
     every epilogue form, split-K slabs; and against fp64."""
     from mclstexp_amd import vit_fused as vf
@@ -60,31 +60,30 @@ def test_gemm_bf16_staggered_kernel_bit_identical(M, N, K, akm, bkm, mode, monke
     outs = []
     # staggered, lockstep (the reference of the bit comparison), then the round-6 persistent pipelined kernel (it declines K ranges
     # under 4 half-tiles: those launches fall through to the staggered one)
-    for stag, pipe in (("1", "0"), ("0", "0"), ("1", "1")):
-        monkeypatch.setenv("MCL_GEMM_STAG", stag)
-        monkeypatch.setenv("MCL_GEMM_PIPE", pipe)
+    for kernel in (vf.KERNEL_NO_PIPE, vf.KERNEL_LOCKSTEP, vf.KERNEL_PIPE):
+        fl = flags | kernel
         f32 = mode.startswith("f32")
         C = torch.full((M, N), 3.0, device=DEV, dtype=torch.float32 if f32 else BF)
         pre = torch.zeros((M, N), device=DEV, dtype=BF)
-        kw = dict(flags=flags)
+        kw = dict(flags=fl)
         if mode == "plain":
             kw.update(alpha=0.5)
         elif mode == "bias":
             kw.update(bias=bias)
         elif mode == "bias_gelu_pre":
-            kw.update(flags=flags | vf.GELU, bias=bias, pre_out=pre, ldp=N)
+            kw.update(flags=fl | vf.GELU, bias=bias, pre_out=pre, ldp=N)
         elif mode == "bias_gelu2":
-            kw.update(flags=flags | vf.GELU | vf.GELU_GRAD_OUT, bias=bias, pre_out=pre, ldp=N)
+            kw.update(flags=fl | vf.GELU | vf.GELU_GRAD_OUT, bias=bias, pre_out=pre, ldp=N)
         elif mode == "gelu_bwd2":
-            kw.update(flags=flags | vf.AUX_IS_GRAD, aux=aux, ldaux=N)
+            kw.update(flags=fl | vf.AUX_IS_GRAD, aux=aux, ldaux=N)
         elif mode == "resid":
             kw.update(bias=bias, resid=res, ldr=N)
         elif mode == "gelu_bwd":
-            kw.update(flags=flags | vf.GELU_BWD, aux=aux, ldaux=N)
+            kw.update(flags=fl | vf.GELU_BWD, aux=aux, ldaux=N)
         elif mode == "f32":
-            kw.update(flags=flags | vf.OUT_F32)
+            kw.update(flags=fl | vf.OUT_F32)
         else:
-            kw.update(flags=flags | vf.OUT_F32, ksplit=8, accumulate=True)
+            kw.update(flags=fl | vf.OUT_F32, ksplit=8, accumulate=True)
         vf.gemm(A, B, C, M, N, K, A.shape[1], B.shape[1], N, **kw)
         torch.cuda.synchronize()
         outs.append((C, pre))

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Serial time of the spot branch: one training step of mclSTExp_Attention with the identity image encoder (features
 supplied), i.e. spot encoder + both projection heads + InfoNCE + Adam incl. the position tables, replayed as ONE HIP
-graph on one stream.  A/B the split-K path of mcl_gemm with MCL_GEMM_SPLITK=0."""
+graph on one stream.  The JSON line records the spot-path switches in effect (ops.SPLIT_K, ops.FUSED_HEAD)."""
 import argparse
 import json
 import os

@@ -65,7 +65,6 @@ def main():
     dxp = torch.empty(B, H // 2, H // 2, 64, device=dev, dtype=torch.bfloat16)
     out["maxpool_bwd_us"] = round(timed(lambda: _lib.check(L.mcl_maxpool3s2_nhwc_bf16_bwd_ld(idx.data_ptr(), gbuf.data_ptr(), 256, dxp.data_ptr(),
                                                                                              B, H // 2, H // 2, 64, st()))), 2)
-    out["MCL_CONV0_WRW_DBG"] = os.environ.get("MCL_CONV0_WRW_DBG", "0")
     print(json.dumps(out), flush=True)
 
 

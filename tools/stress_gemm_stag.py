@@ -25,14 +25,14 @@ for it in range(n_iter):
     A = (torch.rand((K, M) if akm else (M, K), device="cuda") * 2 - 1).to(BF)
     B = (torch.rand((K, N) if bkm else (N, K), device="cuda") * 2 - 1).to(BF)
     outs = []
-    for stag in ("1", "0"):
-        os.environ["MCL_GEMM_STAG"] = stag
+    for kernel in (vf.KERNEL_NO_PIPE, vf.KERNEL_LOCKSTEP):
+        stag = kernel == vf.KERNEL_NO_PIPE
         C = torch.zeros((M, N), device="cuda", dtype=BF)
-        if stag == "1":
+        if stag:
             with torch.cuda.stream(side):                      # memory traffic beside the kernel under test
                 noise.mul_(1.0001)
-        for _ in range(3 if stag == "1" else 1):               # the staggered kernel three times: any run may expose a race
-            vf.gemm(A, B, C, M, N, K, A.shape[1], B.shape[1], N, flags=akm * vf.A_KM | bkm * vf.B_KM)
+        for _ in range(3 if stag else 1):                      # the staggered kernel three times: any run may expose a race
+            vf.gemm(A, B, C, M, N, K, A.shape[1], B.shape[1], N, flags=akm * vf.A_KM | bkm * vf.B_KM | kernel)
             outs.append(C.clone())
     torch.cuda.synchronize()
     ref = outs[-1]
