@@ -7,7 +7,6 @@
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));   // native vector type (the non-temporal builtins reject HIP's float4 class)
 __device__ __forceinline__ float4 nt_load4(const float* q) {
   const f32x4 t = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(q));
   return make_float4(t[0], t[1], t[2], t[3]);

@@ -23,7 +23,6 @@
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int AD = 64;          // head dimension
 constexpr int LP = 129;         // LDS pitch (floats) of a 32 x 128 block
 

@@ -29,14 +29,6 @@ template <> struct Vec<float> {
     *reinterpret_cast<float4*>(p) = make_float4(f[0], f[1], f[2], f[3]);
   }
 };
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float bf2f(unsigned short h) { return __uint_as_float(((unsigned)h) << 16); }
-__device__ __forceinline__ unsigned short f2bf_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7F800000u) == 0x7F800000u) return (unsigned short)(u >> 16);  // inf/nan: truncate
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
-}
 template <> struct Vec<bf16_t> {
   static constexpr int V = 8;
   __device__ static void load(const bf16_t* p, float (&f)[8]) {

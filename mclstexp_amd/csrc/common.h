@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/mclstexp_hip.h"
+#include "device.h"
 
 #define MCL_WAVE 64
 

@@ -40,14 +40,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int CI = 128, CO = 32;
 constexpr int NWAVE = 8;                        // waves per workgroup (two per SIMD), one workgroup per CU
 constexpr int WROW = 2304 + 16;                 // LDS bytes per output channel's 1152 weights (+16: conflict-free fragment reads)
@@ -56,27 +48,9 @@ constexpr int SLAB_ROWS = 34;                   // 32 strip pixels + one halo pi
 constexpr int SLAB_BYTES = SLAB_ROWS * 256;
 constexpr int FRAG_DEPTH = 1;                   // fragment sets requested ahead of the MFMAs (2 and 3 measured no faster)
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-
-__device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float (&sc)[8], const float (&sh)[8]) {
-  unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = fmaxf(fmaf(bf_lo(w[i]), sc[2 * i], sh[2 * i]), 0.0f);
-    const float hi = fmaxf(fmaf(bf_hi(w[i]), sc[2 * i + 1], sh[2 * i + 1]), 0.0f);
-    w[i] = pack2(lo, hi);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // a = relu(x*sc + sh) on one dword (two bf16 channels)
 __device__ __forceinline__ unsigned bn_relu_pair(unsigned w, float sc0, float sc1, float sh0, float sh1) {
-  return pack2(fmaxf(fmaf(bf_lo(w), sc0, sh0), 0.0f), fmaxf(fmaf(bf_hi(w), sc1, sh1), 0.0f));
+  return pack_bf16(fmaxf(fmaf(bf_lo(w), sc0, sh0), 0.0f), fmaxf(fmaf(bf_hi(w), sc1, sh1), 0.0f));
 }
 
 // One staged input row against the kernel rows selected at compile time.  wf = this lane's weight row (+ 16 h): fragment
@@ -161,25 +135,10 @@ __device__ __forceinline__ void row_mfma_dispatch(int m, const unsigned char* wf
   }
 }
 
-// sum over the 32 lanes of each half-wave by DPP (5 VALU instructions, no LDS); the total lands in lanes 16..31 / 48..63
-__device__ __forceinline__ float half_wave_sum(float x) {
-#define MCL_DPP_ADD(ctrl, rmask)                                                                              \
-  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xF, false))
-  MCL_DPP_ADD(0xB1, 0xF);     // quad_perm [1,0,3,2]
-  MCL_DPP_ADD(0x4E, 0xF);     // quad_perm [2,3,0,1]
-  MCL_DPP_ADD(0x141, 0xF);    // row_half_mirror
-  MCL_DPP_ADD(0x140, 0xF);    // row_mirror: every lane of a 16-lane row holds the row sum
-  MCL_DPP_ADD(0x142, 0xA);    // row_bcast15 into rows 1 and 3: + the sum of the row below
-#undef MCL_DPP_ADD
-  return x;
-}
-
 // Completed output row: acc[r] = y[pixel = lane & 31][co = (r & 3) + 8 (r >> 2) + 4 h].  bf16 rounding, running sums of the
 // rounded values (the statistics the consumers' norm1 need), two 16-byte stores per lane.
 // ``orow`` = buffer descriptor of the output image row (exactly its valid bytes): a lane whose pixel lies beyond the image
 // width addresses past the descriptor's range and the hardware drops its stores -- no branch.
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Batch statistics of the output on the matrix cores.  A lane of the accumulator layout owns ONE pixel, so per-channel
 // sums over pixels would be 32 per-lane running sums (no registers left) or a cross-lane reduction per row.  Instead the
@@ -204,7 +163,7 @@ __device__ __forceinline__ void emit_row(const f32x16& a, __amdgpu_buffer_rsrc_t
   const unsigned ooff = (unsigned)px * ldo2 + 16u * (unsigned)(ln >> 5);
   unsigned pk[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) pk[q] = pack2(a[2 * q], a[2 * q + 1]);
+  for (int q = 0; q < 8; ++q) pk[q] = pack_bf16(a[2 * q], a[2 * q + 1]);
   // piece P_q = (pk[2q], pk[2q+1]) = channels 8q + 4h + {0..3}.  Swap pairs (P0, P1) and (P2, P3) between the half-waves: the
   // lower half then holds channels 0-7 / 16-23 of its pixel, the upper half 8-15 / 24-31, each as 16 contiguous bytes.
 #pragma unroll
@@ -295,8 +254,6 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void conv3x3_fwd_rows_kernel(
     // the hardware returns zeros for both, no branch, no address clamp.
     // (lane-derived offsets are recomputed from an opaque copy of the lane id at each use: kept live across the row loop they
     // get spilled, and a scratch reload costs an s_waitcnt vmcnt(0) in the middle of the load / MFMA pipeline)
-    auto opaque_lane = [&]() { int ln = lane; asm volatile("" : "+v"(ln)); return ln; };
-
     // two staging register sets: while row j is multiplied, row j+1 (requested one row earlier) is transformed in the MFMA
     // shadow and row j+2 is in flight from HBM -- 18 KB per wave outstanding, what the HBM latency needs at 8 waves per CU
     u32x4 vA[9], vB[9];
@@ -304,7 +261,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void conv3x3_fwd_rows_kernel(
     // memory access -- a branch around the loads would make their destination registers phi values, which the compiler
     // resolves with copies behind s_waitcnt vmcnt(0))
     auto load_row = [&](int j, u32x4 (&v)[9]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       // vector offsets only (the scalar soffset operand is not range-checked) and never negative: a wrapped 32-bit offset plus
       // an immediate must not depend on how wide the hardware adds them.  Only (x0 = 0, first pixel row, tt = 0) has x = -1:
       // it reads pixel 0 instead and write_row stores zeros for it anyway.
@@ -330,7 +287,7 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void conv3x3_fwd_rows_kernel(
     // v[] holds a2 = relu(bn(z)) already.  Slab row i = sr + 4 tt, swizzled chunk cc ^ (i & 15) = (cc ^ sr) ^ 4 (tt & 3): four
     // lane-constant bases + tt * 1024.  The conv's zero padding applies to a2, not to z: out-of-image pixels store zeros.
     auto write_row = [&](u32x4 (&v)[9]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       const int sr = ln >> 4, cc = ln & 15, wbase = sr * 256 + ((cc ^ sr) << 4);
 #pragma unroll
       for (int tt = 0; tt < 9; ++tt) {
@@ -366,10 +323,10 @@ __global__ __launch_bounds__(64 * NWAVE, 2) void conv3x3_fwd_rows_kernel(
       row_mfma_dispatch(m, wf, slab, pbase, aN, aC, aP, X, coef4);                                             \
       if ((m & 4))                                                                           \
         emit_row<true>(aP, __builtin_amdgcn_make_buffer_rsrc(out + (img + j - 1) * W * ldo, 0, orow_bytes, 0x00020000), \
-                       opaque_lane(), x0, W, ldo2, scratch, st);                                               \
+                       opaque_lane(lane), x0, W, ldo2, scratch, st);                                           \
       if (j == H - 1 && (m & 2))                                                                               \
         emit_row<true>(aC, __builtin_amdgcn_make_buffer_rsrc(out + (img + j) * W * ldo, 0, orow_bytes, 0x00020000),    \
-                       opaque_lane(), x0, W, ldo2, scratch, st);                                               \
+                       opaque_lane(lane), x0, W, ldo2, scratch, st);                                           \
       if (more) write_row(X);                                                                \
       aP = aC;                                                                                                 \
       aC = aN;                                                                                                 \

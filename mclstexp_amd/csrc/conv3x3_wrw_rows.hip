@@ -28,22 +28,9 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int WR_NWAVE = 8;                       // two row streams x four channel quarters
 constexpr int WR_MN = 32 * 9 * 128;               // elements of dW2
 constexpr int WR_RED_BYTES = 4 * 9 * 16 * 64 * 4; // the second stream's accumulators in LDS at the end: 147,456 B
-
-__device__ __forceinline__ unsigned wr_pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
 
 // 8 consecutive pixels (from pixel row p0 + 8 h of a [pixel][64 B] tile) of channel l & 31: two transposing reads, each a
 // 4-pixel x 16-channel block per 16-lane group.  ``la`` = this lane's byte offset inside the first block.
@@ -97,12 +84,10 @@ __global__ __launch_bounds__(64 * WR_NWAVE, 2) void conv3x3_wrw_rows_kernel(
     const int chunk = u % nchunk, b = u / nchunk;
     const int j0 = chunk * rc, j1 = min(H, j0 + rc);
     const long long img = (long long)b * H;
-    auto opaque_lane = [&]() { int ln = lane; asm volatile("" : "+v"(ln)); return ln; };
-
     // z row r, this wave's channel quarter: chunk tt covers pixels 16 tt + (ln >> 2), 16 bytes at (ln & 3) of the 64-byte
     // quarter row.  Rows past the unit read through a zero-size descriptor (zeros, no memory access).
     auto load_z = [&](int r, u32x4 (&v)[NZ]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<bf16_t*>(z) + (img + min(r, H - 1)) * W * 128, 0, r < j1 ? zrow_bytes : 0u, 0x00020000);
       const unsigned off = (unsigned)(ln >> 2) * 256u + (unsigned)q * 64u + (unsigned)(ln & 3) * 16u;
@@ -112,7 +97,7 @@ __global__ __launch_bounds__(64 * WR_NWAVE, 2) void conv3x3_wrw_rows_kernel(
     // a2 = relu(bn2(z)) of the row -> a2buf; pixels beyond the image width are zeros (their z reads returned zeros, but
     // relu(shift) need not be zero)
     auto write_a2 = [&](const u32x4 (&v)[NZ]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
 #pragma unroll
       for (int tt = 0; tt < NZ; ++tt) {
         const int x = 16 * tt + (ln >> 2);
@@ -121,14 +106,14 @@ __global__ __launch_bounds__(64 * WR_NWAVE, 2) void conv3x3_wrw_rows_kernel(
         for (int d = 0; d < 4; ++d) {
           const float lo = fmaxf(fmaf(__uint_as_float(w[d] << 16), sc[2 * d], sh[2 * d]), 0.0f);
           const float hi = fmaxf(fmaf(__uint_as_float(w[d] & 0xFFFF0000u), sc[2 * d + 1], sh[2 * d + 1]), 0.0f);
-          w[d] = x < W ? wr_pack2(lo, hi) : 0u;
+          w[d] = x < W ? pack_bf16(lo, hi) : 0u;
         }
         *reinterpret_cast<uint4*>(a2buf + x * 64 + (ln & 3) * 16) = make_uint4(w[0], w[1], w[2], w[3]);
       }
     };
     // dy row y: chunk tt covers pixel index i = 16 tt + (ln >> 2) (x = i - 1).  Rows outside the image: zero-size descriptor.
     auto load_dy = [&](int y, u32x4 (&d)[ND]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       const bool inr = y >= 0 && y < H;
       const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<bf16_t*>(dy) + (img + min(max(y, 0), H - 1)) * W * lddy, 0, inr ? dyrow_bytes : 0u, 0x00020000);
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(64 * WR_NWAVE, 2) void conv3x3_wrw_rows_kernel(
       }
     };
     auto write_dy = [&](unsigned char* slot, const u32x4 (&d)[ND]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
 #pragma unroll
       for (int tt = 0; tt < ND; ++tt) {
         const int i = 16 * tt + (ln >> 2), x = i - 1;
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(64 * WR_NWAVE, 2) void conv3x3_wrw_rows_kernel(
       __builtin_amdgcn_sched_barrier(0);
       // ---- 9 NKS MFMAs: tap (ky, kx) reads dy row r + 1 - ky (slots C, B, A) from pixel index 16 ks + 2 - kx
       {
-        const int ln = opaque_lane();
+        const int ln = opaque_lane(lane);
         const int lo_ = (8 * (ln >> 5) + ((ln & 15) >> 2)) * 64 + 32 * ((ln >> 4) & 1) + 8 * (ln & 3);
         const unsigned char* pa = a2buf + lo_;
         const unsigned char* p0 = sC + lo_;

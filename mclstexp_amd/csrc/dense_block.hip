@@ -28,15 +28,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned long long u64;
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int DB_MAXL = 24;
 constexpr int HW = 49, MAPW = 7, PW = 9;          // pixels per image, map width, padded width
 constexpr int ZERO_ROW = PW * PW;                 // a2 tile row of zeros (pixels 49..63 of the second MFMA tile)
@@ -68,15 +59,8 @@ struct DBArgs {
   DBLayer ly[DB_MAXL];
 };
 
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ float round_bf16(float v) { return bf_lo(pack2(v, 0.0f)); }
-
-__device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float* sc, const float* sh) {
+// a = relu(x*sc + sh) on one 16-byte chunk (8 channels); sc and sh are read as two float4 each
+__device__ __forceinline__ uint4 bn_relu_chunk_f4(uint4 v, const float* sc, const float* sh) {
   unsigned w[4] = {v.x, v.y, v.z, v.w};
   const float4 s0 = *reinterpret_cast<const float4*>(sc), s1 = *reinterpret_cast<const float4*>(sc + 4);
   const float4 t0 = *reinterpret_cast<const float4*>(sh), t1 = *reinterpret_cast<const float4*>(sh + 4);
@@ -86,7 +70,7 @@ __device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float* sc, const f
   for (int i = 0; i < 4; ++i) {
     const float lo = fmaxf(fmaf(bf_lo(w[i]), s[2 * i], t[2 * i]), 0.0f);
     const float hi = fmaxf(fmaf(bf_hi(w[i]), s[2 * i + 1], t[2 * i + 1]), 0.0f);
-    w[i] = pack2(lo, hi);
+    w[i] = pack_bf16(lo, hi);
   }
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
@@ -147,7 +131,7 @@ __device__ __forceinline__ void mul_chunk(const unsigned char* A, const u32x4 (&
     }
     if (STAGE && k0 == 0) {
 #pragma unroll
-      for (int i = 0; i < 3; ++i) o[i] = bn_relu_chunk(make_uint4(xv[i][0], xv[i][1], xv[i][2], xv[i][3]), tsc, tsh);
+      for (int i = 0; i < 3; ++i) o[i] = bn_relu_chunk_f4(make_uint4(xv[i][0], xv[i][1], xv[i][2], xv[i][3]), tsc, tsh);
     }
 #pragma unroll
     for (int kk = 0; kk < NH; ++kk) {
@@ -164,7 +148,7 @@ __device__ __forceinline__ void mul_chunk(const unsigned char* A, const u32x4 (&
     }
     if (rr == 0)                                                // rows 48..63: only row 48 exists
       *reinterpret_cast<uint4*>(An + 48 * 256 + (cc << 4)) =
-          bn_relu_chunk(make_uint4(xv[3][0], xv[3][1], xv[3][2], xv[3][3]), tsc, tsh);
+          bn_relu_chunk_f4(make_uint4(xv[3][0], xv[3][1], xv[3][2], xv[3][3]), tsc, tsh);
   }
 }
 
@@ -244,20 +228,12 @@ __global__ __launch_bounds__(256, 1) void dense_block_fwd_kernel(DBArgs a) {
       const bool xlive = cc * 8 < w;
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-#ifdef DB_EXP_NOX
-        xv[i] = u32x4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, (unsigned)c};
-#else
         xv[i] = __builtin_amdgcn_raw_buffer_load_b128(xrs, xlive ? xoff[i] + (unsigned)c0 * 2u : 0xFFFFF000u, 0, 0);
-#endif
       // lane (n, h), k-step kk < w/16: channels c0 + h*w/2 + 8*kk .. +8 of row n = wave*32 + l31, at its packed position
       const unsigned wb = (unsigned)c0 * 256u + (unsigned)(wave * (w >> 4)) * 1024u + (unsigned)lane * 16u;
 #pragma unroll
       for (int kk = 0; kk < 8; ++kk)
-#ifdef DB_EXP_NOW
-        wv[kk] = u32x4{0x3c003c00u, 0x3c003c00u, wb, (unsigned)kk};
-#else
         wv[kk] = __builtin_amdgcn_raw_buffer_load_b128(wrs, (w > 0 && kk * 16 < w) ? wb + kk * 1024u : 0xFFFFF000u, 0, 0);
-#endif
     };
     // (debug: cycle stamps of one workgroup's chunk loop, K = 960: [chunk][multiplied + staged, loads issued, barrier passed])
     unsigned long long* cst = (a.dbg && img == 0 && tid == 0 && K == 960) ? a.dbg + (long long)B * a.L * 8 : nullptr;
@@ -269,7 +245,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_fwd_kernel(DBArgs a) {
       for (int i = 0; i < 4; ++i) {
         if (i < 3 || rr == 0) {
           const int r = rr + 16 * i;
-          const uint4 v = bn_relu_chunk(make_uint4(xv[i][0], xv[i][1], xv[i][2], xv[i][3]), tab + kc, tab + 1024 + kc);
+          const uint4 v = bn_relu_chunk_f4(make_uint4(xv[i][0], xv[i][1], xv[i][2], xv[i][3]), tab + kc, tab + 1024 + kc);
           *reinterpret_cast<uint4*>(At + r * 256 + ((cc ^ (r & 15)) << 4)) = v;
         }
       }
@@ -389,7 +365,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_fwd_kernel(DBArgs a) {
         for (int q = 0; q < 4; ++q) {
           const float lo = fmaxf(fmaf(rv[px * 32 + c0 + 2 * q], tab[k + 2 * q], tab[1024 + k + 2 * q]), 0.0f);
           const float hi = fmaxf(fmaf(rv[px * 32 + c0 + 2 * q + 1], tab[k + 2 * q + 1], tab[1024 + k + 2 * q + 1]), 0.0f);
-          w[q] = pack2(lo, hi);
+          w[q] = pack_bf16(lo, hi);
         }
         *reinterpret_cast<uint4*>(At + px * 256 + (((c0 >> 3) ^ (px & 15)) << 4)) = make_uint4(w[0], w[1], w[2], w[3]);
       }
@@ -522,7 +498,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_fwd_kernel(DBArgs a) {
       if (r < HW) {
         const uint4 v = *reinterpret_cast<const uint4*>(zt + r * 256 + ((cc ^ (r & 15)) << 4));
         const int pr = (r / MAPW + 1) * PW + (r % MAPW) + 1;
-        *reinterpret_cast<uint4*>(a2t + pr * 256 + ((cc ^ (pr & 15)) << 4)) = bn_relu_chunk(v, tab2 + cc * 8, tab2 + 128 + cc * 8);
+        *reinterpret_cast<uint4*>(a2t + pr * 256 + ((cc ^ (pr & 15)) << 4)) = bn_relu_chunk_f4(v, tab2 + cc * 8, tab2 + 128 + cc * 8);
       }
     }
     __syncthreads();
@@ -570,7 +546,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_fwd_kernel(DBArgs a) {
       }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
-        pk[q] = pack2(v[2 * q], v[2 * q + 1]);
+        pk[q] = pack_bf16(v[2 * q], v[2 * q + 1]);
         rv[px * 32 + c0 + 2 * q] = bf_lo(pk[q]);
         rv[px * 32 + c0 + 2 * q + 1] = bf_hi(pk[q]);
       }
@@ -764,9 +740,6 @@ struct DBBArgs {
   DBBLayer ly[DB_MAXL];
 };
 
-__device__ __forceinline__ float bf2f_(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ bf16_t f2bf_(float f) { return (bf16_t)(pack2(f, 0.0f) & 0xFFFFu); }
-
 #define DBB_STAMP(k)                                                                                     \
   do {                                                                                                   \
     if (a.dbg && tid == 0) a.dbg[((long long)img * a.L + l) * 8 + (k)] = wall_clock64();                 \
@@ -845,7 +818,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_bwd_kernel(DBBArgs a) {
             const float gf = e ? bf_hi(gw[u]) : bf_lo(gw[u]);
             o[e] = gf - fmaf(ka, xf, kb);
           }
-          gw[u] = pack2(o[0], o[1]);
+          gw[u] = pack_bf16(o[0], o[1]);
         }
         v = make_uint4(gw[0], gw[1], gw[2], gw[3]);
       }
@@ -890,10 +863,10 @@ __global__ __launch_bounds__(256, 1) void dense_block_bwd_kernel(DBBArgs a) {
         for (int r = 0; r < 16; ++r) {
           const int px = mb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
           if (px < HW) {
-            const float zv = bf2f_(zt[px * 128 + c2ch]);
+            const float zv = bf2f(zt[px * 128 + c2ch]);
             const float gi = fmaf(zv, sc2, sh2) > 0.0f ? acc[mb][r] : 0.0f;
-            const bf16_t gb = f2bf_(gi);
-            const float gr = bf2f_(gb);                                // the sums are those of the stored (rounded) g2
+            const bf16_t gb = f2bf(gi);
+            const float gr = bf2f(gb);                                // the sums are those of the stored (rounded) g2
             s1 += gr;
             s2 = fmaf(gr, (zv - mu2) * rs2, s2);
             reinterpret_cast<bf16_t*>(g2t + px * 256 + (((c2ch >> 3) ^ (px & 15)) << 4))[c2ch & 7] = gb;
@@ -971,7 +944,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_bwd_kernel(DBBArgs a) {
         const int e0 = 2 * u, e1 = 2 * u + 1;
         const float d_lo = tv[0][e0] * (bf_lo(gw[u]) - tv[1][e0] - (bf_lo(zw[u]) - tv[2][e0]) * tv[3][e0] * tv[4][e0]);
         const float d_hi = tv[0][e1] * (bf_hi(gw[u]) - tv[1][e1] - (bf_hi(zw[u]) - tv[2][e1]) * tv[3][e1] * tv[4][e1]);
-        o[u] = pack2(d_lo, d_hi);
+        o[u] = pack_bf16(d_lo, d_hi);
       }
       const uint4 ov = make_uint4(o[0], o[1], o[2], o[3]);
       *reinterpret_cast<uint4*>(gp) = ov;
@@ -1058,13 +1031,13 @@ __global__ __launch_bounds__(256, 1) void dense_block_bwd_kernel(DBBArgs a) {
             const int px = mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
             const bool valid = mt == 0 || px < HW;
             const int pc = valid ? px : HW - 1;                       // (a padding row reads a real row: finite values, da = 0)
-            const float xv = bf2f_(reinterpret_cast<const bf16_t*>(xw_ + pc * 64)[l31]);
+            const float xv = bf2f(reinterpret_cast<const bf16_t*>(xw_ + pc * 64)[l31]);
             const float gi = fmaf(xv, sc, sh) > 0.0f ? da[mt][r] : 0.0f;
             s1 += gi;
             s2 = fmaf(gi, xv, s2);
-            const float delta = bf2f_(f2bf_(fmaf(sc, gi, fmaf(ka, xv, kb))));
+            const float delta = bf2f(f2bf(fmaf(sc, gi, fmaf(ka, xv, kb))));
             bf16_t* gp = Gt + pc * 1024 + n;
-            const bf16_t gnew = f2bf_(bf2f_(*gp) + delta);
+            const bf16_t gnew = f2bf(bf2f(*gp) + delta);
             if (valid) *gp = gnew;
           }
         s2 = rs * fmaf(-mu, s1, s2);
@@ -1161,7 +1134,7 @@ __global__ __launch_bounds__(256, 1) void dense_block_bwd_kernel(DBBArgs a) {
           const float gf = e ? bf_hi(gw[u]) : bf_lo(gw[u]);
           o[e] = gf - fmaf(ka, xf, kb);
         }
-        gw[u] = pack2(o[0], o[1]);
+        gw[u] = pack_bf16(o[0], o[1]);
       }
       *reinterpret_cast<uint4*>(gb_ + (long long)p * Ct + c) = make_uint4(gw[0], gw[1], gw[2], gw[3]);
     }

@@ -22,20 +22,7 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int TN = 128, TK = 128;   // input channels, bottleneck channels per tile (pixels per tile: template TMv)
-
-__device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ bf16_t f2bf(float f) {
-  const f32x2 v = {f, 0.0f};
-  return (bf16_t)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t)) & 0xFFFFu);
-}
 
 // MODE 0: reduce (partials of sum g, sum g*xhat)      MODE 1: dx accumulate
 // MODE 2: ONE pass -- gbuf += gamma*rstd*g (the data-dependent term of dx) AND the partials of the two sums.  The layer's own
@@ -727,25 +714,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_bwd_kernel(const bf16_t* __res
 constexpr int BR_NWAVE = 8;                       // waves per workgroup (two per SIMD)
 constexpr int BR_SLOT = 34 * 64;                  // one dy row of the strip: 34 pixels x 32 channels bf16
 constexpr int BR_RING = 4 * BR_SLOT;              // rows jo-1, jo, jo+1 in use + the one being written
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned br_pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-
-// sum over the 32 lanes of each half-wave by DPP; the total lands in lanes 16..31 / 48..63
-__device__ __forceinline__ float br_half_wave_sum(float x) {
-#define MCL_DPP_ADD(ctrl, rmask) x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xF, false))
-  MCL_DPP_ADD(0xB1, 0xF);     // quad_perm [1,0,3,2]
-  MCL_DPP_ADD(0x4E, 0xF);     // quad_perm [2,3,0,1]
-  MCL_DPP_ADD(0x141, 0xF);    // row_half_mirror
-  MCL_DPP_ADD(0x140, 0xF);    // row_mirror
-  MCL_DPP_ADD(0x142, 0xA);    // row_bcast15 into rows 1 and 3
-#undef MCL_DPP_ADD
-  return x;
-}
 
 // memory order <-> accumulator order of a lane's 16 channels (8 dwords): an involution (see conv3x3_rows.hip emit_row)
 __device__ __forceinline__ void br_swap8(unsigned (&w)[8]) {
@@ -834,12 +802,10 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
     const int j0 = chunk * rc, j1 = min(H, j0 + rc);
     const int jd1 = min(H, j1 + 1);                              // dy rows [max(j0 - 1, 0), jd1) are needed
     const long long img = (long long)b * H;
-    auto opaque_lane = [&]() { int ln = lane; asm volatile("" : "+v"(ln)); return ln; };
-
     // dy row jr of the strip -> 3 chunks per lane: pixel i = (ln >> 2) + 16 tt, 16-byte chunk ln & 3.  Rows outside
     // [0, jd1) read through a zero-size descriptor (zeros, no memory access); x = -1 reads pixel 0 and is zeroed at the write.
     auto load_dy = [&](int jr, u32x4 (&d)[3]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       const bool inr = jr >= 0 && jr < jd1;
       const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<bf16_t*>(dy) + (img + min(max(jr, 0), H - 1)) * W * lddy, 0, inr ? dyrow_bytes : 0u, 0x00020000);
@@ -850,7 +816,7 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
       }
     };
     auto write_dy = [&](int jr, const u32x4 (&d)[3]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       unsigned char* slot = ring + (jr & 3) * BR_SLOT;
 #pragma unroll
       for (int tt = 0; tt < 3; ++tt) {
@@ -863,7 +829,7 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
     };
     // z row jo of this lane's pixel, quarter q, memory order: 16 bytes at 16 h and at 32 + 16 h of the 64-byte quarter row
     auto load_z = [&](int jo, u32x4 (&zr)[2]) {
-      const int ln = opaque_lane();
+      const int ln = opaque_lane(lane);
       const __amdgpu_buffer_rsrc_t row = __builtin_amdgcn_make_buffer_rsrc(
           const_cast<bf16_t*>(z) + (img + min(jo, H - 1)) * W * 128, 0, jo < j1 ? zrow_bytes : 0u, 0x00020000);
       const unsigned off = (unsigned)(x0 + (ln & 31)) * 256u + (unsigned)q * 64u + 16u * (unsigned)(ln >> 5);
@@ -909,7 +875,7 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
       else br_row_mfma<false, false>(ring, jo, foff, breg, acc);                                                \
       /* epilogue: mask, round, sums, store */                                                                  \
       {                                                                                                         \
-        const int ln = opaque_lane();                                                                           \
+        const int ln = opaque_lane(lane);                                                                       \
         const int px = x0 + (ln & 31);                                                                          \
         unsigned zw[8] = {ZX[0][0], ZX[0][1], ZX[0][2], ZX[0][3], ZX[1][0], ZX[1][1], ZX[1][2], ZX[1][3]};      \
         br_swap8(zw);                                                                                           \
@@ -920,7 +886,7 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
           const float z0 = __uint_as_float(zw[d] << 16), z1 = __uint_as_float(zw[d] & 0xFFFF0000u);             \
           const float g0 = fmaf(z0, c4.x, c4.y) > 0.0f ? acc[2 * d] : 0.0f;                                     \
           const float g1 = fmaf(z1, c4.z, c4.w) > 0.0f ? acc[2 * d + 1] : 0.0f;                                 \
-          gw8[d] = br_pack2(g0, g1);                                                                            \
+          gw8[d] = pack_bf16(g0, g1);                                                                           \
           const float r0 = __uint_as_float(gw8[d] << 16), r1 = __uint_as_float(gw8[d] & 0xFFFF0000u);           \
           s1[2 * d] += r0;                                                                                      \
           s2[2 * d] = fmaf(r0, z0, s2[2 * d]);                                                                  \
@@ -953,8 +919,8 @@ __global__ __launch_bounds__(64 * BR_NWAVE, 2) void conv3x3_bwd_rows_kernel(
     const float vmask = x0 + l31 < W ? 1.0f : 0.0f;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      s1[r] = br_half_wave_sum(s1[r] * vmask);
-      s2[r] = br_half_wave_sum(s2[r] * vmask);
+      s1[r] = half_wave_sum(s1[r] * vmask);
+      s2[r] = half_wave_sum(s2[r] * vmask);
     }
     if (l31 == 31) {
 #pragma unroll

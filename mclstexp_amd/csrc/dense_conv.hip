@@ -20,35 +20,8 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int BN = 128;  // bottleneck width (bn_size * growth_rate)
 constexpr int BK = 64;   // input channels per stage (128-byte LDS rows)
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ float round_bf16(float v) { return bf_lo(pack2(v, 0.0f)); }
-
-// a = relu(x*sc + sh) on one 16-byte chunk (8 channels)
-__device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float (&sc)[8], const float (&sh)[8]) {
-  unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float lo = fmaxf(fmaf(bf_lo(w[i]), sc[2 * i], sh[2 * i]), 0.0f);
-    const float hi = fmaxf(fmaf(bf_hi(w[i]), sc[2 * i + 1], sh[2 * i + 1]), 0.0f);
-    w[i] = pack2(lo, hi);
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
 
 // WM wave-rows of RW (64 or 32) rows each, two wave-columns of 64 channels: BM = WM*RW rows, 128*WM threads.  <2, 32> is
 // the small-map form of <1, 64>: the same 64-row tile and LDS footprint but four waves instead of two per workgroup
@@ -425,10 +398,7 @@ constexpr int C3_IN = 128, C3_OUT = 32, T3 = 128;   // channels in / out, pixels
 // batches of NB independent global loads per thread (a load -> transform -> store loop would serialise one full
 // memory latency per pass: the slab is 10-16 passes).
 // independent global loads in flight per thread and batch (measured at cfg2: 8 beats 4 by 2 %, 16 loses 3 %)
-#ifndef MCL_SLAB_NB
-#define MCL_SLAB_NB 8
-#endif
-constexpr int SLAB_NB = MCL_SLAB_NB;
+constexpr int SLAB_NB = 8;
 template <int NB>
 __device__ __forceinline__ void stage_slab(unsigned char* lds, const bf16_t* __restrict__ z, int p0, long long S,
                                            int W, int nrow, int tid, const float (&sc)[8], const float (&sh)[8]) {
@@ -564,7 +534,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_fwd_kernel(const bf16_t* __res
   }
   unsigned pk[8];
 #pragma unroll
-  for (int q = 0; q < 8; ++q) pk[q] = pack2(v[2 * q], v[2 * q + 1]);
+  for (int q = 0; q < 8; ++q) pk[q] = pack_bf16(v[2 * q], v[2 * q + 1]);
   if (p < S) {
     *reinterpret_cast<uint4*>(out + p * ldo + c0) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
     *reinterpret_cast<uint4*>(out + p * ldo + c0 + 8) = make_uint4(pk[4], pk[5], pk[6], pk[7]);
@@ -691,7 +661,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_wrw_ky_kernel(const bf16_t* __
                                                                 const float* __restrict__ rstd, int ntile, int G,
                                                                 float* __restrict__ wpart) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[W3K_LDS];
-  typedef short v4s __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   // XCD-aware decode (block id % 8 = XCD): the three kernel rows of one pixel group sit in consecutive slots of one XCD
@@ -906,17 +875,9 @@ constexpr int C0_OUT = 64, C0_K = 7, C0_KP = 24;        // output channels, kern
 // behind three loads that each waited for the previous one.)
 constexpr int C0_P0 = 16;
 __host__ __device__ inline int c0_pw(int W) { return ((C0_P0 + 3 * W + 24 + 7) / 8) * 8; }   // row pitch in elements (16-byte rows)
-typedef unsigned u32x4_d __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void c0_dma16(u32x4_d rsrc, unsigned voff, unsigned dst) {     // 64 lanes x 16 B -> LDS dst + 16 lane
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(dst)
-               : "memory");
-}
-__device__ __forceinline__ u32x4_d c0_rsrc(const void* base, unsigned bytes) {
+__device__ __forceinline__ u32x4 c0_rsrc(const void* base, unsigned bytes) {
   const unsigned long long a = (unsigned long long)base;
-  return u32x4_d{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
+  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, bytes, 0x00020000u};
 }
 // Rows r = wave, wave + 4, ... of the 9-row slab of tile (n, oy0): each row W * 6 bytes = cpr 16-byte chunks, 64 per instruction
 // (lanes past the row's last chunk are switched off: they must not write into the right padding).
@@ -926,10 +887,10 @@ __device__ __forceinline__ void c0_dma_slab(const bf16_t* __restrict__ x, int n,
   for (int r = wave; r < 9; r += 4) {
     const int iy = 2 * oy0 - 3 + r;
     const bool inside = iy >= 0 && iy < H;
-    const u32x4_d rs = c0_rsrc(x + ((long long)(n * H + (inside ? iy : 0)) * W) * 3, inside ? (unsigned)(W * 6) : 0u);
+    const u32x4 rs = c0_rsrc(x + ((long long)(n * H + (inside ? iy : 0)) * W) * 3, inside ? (unsigned)(W * 6) : 0u);
     const unsigned dst = slab_lds + (unsigned)(r * PW + C0_P0) * 2u;
     for (int c0 = 0; c0 < cpr; c0 += 64)
-      if (c0 + lane < cpr) c0_dma16(rs, (unsigned)(c0 + lane) * 16u, dst + (unsigned)c0 * 16u);
+      if (c0 + lane < cpr) buffer_lds16(rs, (unsigned)(c0 + lane) * 16u, dst + (unsigned)c0 * 16u);
   }
 }
 
@@ -1088,7 +1049,6 @@ __global__ __launch_bounds__(256, 2) void conv0_wrw_kernel(const bf16_t* __restr
   // c ^ (((r >> 1) & 1) << 2) (the four rows of a transposing read then cover all 64 banks).  A fragments -- 8 consecutive pixels
   // of one channel -- are two ds_read_b64_tr_b16; the former [co][pixel] tile cost 56 two-byte LDS stores per thread and tile.
   unsigned char* dyt = lds + slab_bytes;
-  typedef short v4s __attribute__((ext_vector_type(4)));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = lane >> 5, l31 = lane & 31;
   const int mt = wave & 1, kt0 = (wave >> 1) * 3;

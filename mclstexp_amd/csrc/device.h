@@ -1,0 +1,133 @@
+// Device types and helpers shared by the gfx950 kernels (included from common.h).  A helper that rounds or loads
+// differently from the ones here keeps a name of its own in its file (gemm.hip f2bf_rne_finite: no inf / NaN handling;
+// dense_block.hip bn_relu_chunk_f4; the buffer descriptors c0_rsrc / raw_rsrc).
+#pragma once
+#include <hip/hip_runtime.h>
+
+typedef unsigned short bf16_t;                                   // bf16 bits
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef short bf16x8 __attribute__((ext_vector_type(8)));        // MFMA bf16 operand
+typedef short v4s __attribute__((ext_vector_type(4)));           // ds_read_b64_tr_b16 result
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));         // the non-temporal builtins reject HIP's float4 class
+typedef float f32x16 __attribute__((ext_vector_type(16)));       // 32x32 MFMA accumulator
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));      // 16-byte chunk; buffer descriptor
+typedef unsigned long long u64;
+
+#define MCL_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
+#define MCL_GLBP(p) ((const __attribute__((address_space(1))) void*)(p))
+
+// ---- bf16 <-> fp32.  pack_bf16 / f2bf / round_bf16 round to nearest even in hardware (v_cvt_pk_bf16_f32).
+__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
+__device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
+__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
+  const f32x2 v = {a, b};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));  // v_cvt_pk_bf16_f32 (RNE)
+}
+__device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf16(f, 0.0f) & 0xFFFFu); }
+__device__ __forceinline__ float round_bf16(float v) { return bf_lo(pack_bf16(v, 0.0f)); }
+// round to nearest even in software (inf / NaN truncated), in the low 16 bits of the result
+__device__ __forceinline__ unsigned f2bf_rne(float f) {
+  unsigned u = __float_as_uint(f);
+  if ((u & 0x7F800000u) == 0x7F800000u) return u >> 16;   // inf / nan: truncate
+  u += 0x7FFFu + ((u >> 16) & 1u);
+  return u >> 16;
+}
+
+// one 16-byte chunk = 8 bf16 channels
+__device__ __forceinline__ void unpack8(uint4 v, float (&f)[8]) {
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    f[2 * i] = bf_lo(w[i]);
+    f[2 * i + 1] = bf_hi(w[i]);
+  }
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+  unsigned w[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {   // pack_bf16 written out: a call to it here changes the code of pool.hip's kernels
+    const f32x2 v = {f[2 * i], f[2 * i + 1]};
+    w[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// a = relu(x*sc + sh) on one 16-byte chunk (8 channels)
+__device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float (&sc)[8], const float (&sh)[8]) {
+  unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float lo = fmaxf(fmaf(bf_lo(w[i]), sc[2 * i], sh[2 * i]), 0.0f);
+    const float hi = fmaxf(fmaf(bf_hi(w[i]), sc[2 * i + 1], sh[2 * i + 1]), 0.0f);
+    w[i] = pack_bf16(lo, hi);
+  }
+  return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// ---- lanes
+// number of set bits of ``mask`` below this lane
+__device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {
+  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
+}
+
+// sum over the 32 lanes of each half-wave by DPP (5 VALU instructions, no LDS); the total lands in lanes 16..31 / 48..63
+__device__ __forceinline__ float half_wave_sum(float x) {
+#define MCL_DPP_ADD(ctrl, rmask)                                                                              \
+  x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), ctrl, rmask, 0xF, false))
+  MCL_DPP_ADD(0xB1, 0xF);     // quad_perm [1,0,3,2]
+  MCL_DPP_ADD(0x4E, 0xF);     // quad_perm [2,3,0,1]
+  MCL_DPP_ADD(0x141, 0xF);    // row_half_mirror
+  MCL_DPP_ADD(0x140, 0xF);    // row_mirror: every lane of a 16-lane row holds the row sum
+  MCL_DPP_ADD(0x142, 0xA);    // row_bcast15 into rows 1 and 3: + the sum of the row below
+#undef MCL_DPP_ADD
+  return x;
+}
+
+// the lane id, made opaque to the compiler: everything derived from it is recomputed where it is used instead of being
+// hoisted out of the loop into live registers
+__device__ __forceinline__ int opaque_lane(int lane) {
+  asm volatile("" : "+v"(lane));
+  return lane;
+}
+
+// ---- LDS-DMA: every lane fetches 16 (glds4: 4) bytes; the wave's bytes land lane-linear at the wave-uniform LDS byte
+// address ``dst`` (M0) -- no VGPR round trip.  Inline asm on purpose: hipcc cannot prove that a DMA into one LDS buffer
+// does not alias the LDS being read from another and would drain vmcnt(0) -- the whole prefetch -- mid-tile.  Hidden from
+// its bookkeeping, the DMA is covered by the caller's explicit vmcnt + barrier.
+__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(src), "s"(dst)
+               : "memory");
+}
+// saddr form: wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset
+// (M0 is not saved / restored here: nothing else in its callers, gemm_bf16.hip and infonce_fused.hip, uses it -- checked
+// in the ISA -- and the two extra s_mov per piece are issue slots of a lone wave.)
+// The "m0" clobber draws hipcc's "inline asm clobber list contains reserved registers: m0" at every use.
+__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned dst) {
+  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0"
+               :
+               : "s"(sbase), "v"(voff), "s"(dst)
+               : "memory", "m0");
+}
+__device__ __forceinline__ void glds4(const void* src, unsigned dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(src), "s"(dst)
+               : "memory");
+}
+// buffer form: every lane fetches 16 bytes at its own 32-bit byte offset ``voff`` from the buffer descriptor ``rsrc``.  A
+// chunk beyond the descriptor's num_records is out of range: it lands in LDS as ZEROS and touches no memory (checked on
+// MI355X), so ragged tiles need no branch.
+__device__ __forceinline__ void buffer_lds16(u32x4 rsrc, unsigned voff, unsigned dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep)
+               : "v"(voff), "s"(rsrc), "s"(dst)
+               : "memory");
+}

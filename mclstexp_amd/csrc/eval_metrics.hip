@@ -25,10 +25,6 @@ constexpr int HEG_CAP = 2048;      // candidates ranked in LDS; more -> ranked a
 template <typename T>
 __device__ __forceinline__ double ld64(const T* p) { return (double)*p; }
 
-__device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // writes r, true_mean and the per-gene mean squared / absolute error (work[s][0][g], work[s][1][g])
 template <typename TP, typename TT>
 __global__ __launch_bounds__(STAT_WAVES * 64) void expr_gene_stats_kernel(

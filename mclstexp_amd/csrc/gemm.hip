@@ -20,9 +20,6 @@ namespace {
 
 constexpr int BM = 64, BN = 64, BK = 32, NT = 256;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-
 struct GemmP {
   int M, N, K;
   const float* A; long long sAm, sAk, sAb;
@@ -39,7 +36,7 @@ struct GemmP {
   const float* flt_thr; int* flt_cnt; float* flt_val; int* flt_idx; int flt_cap;
 };
 
-__device__ __forceinline__ unsigned short f2bf(float f) {  // round-to-nearest-even
+__device__ __forceinline__ unsigned short f2bf_rne_finite(float f) {  // round-to-nearest-even; no inf/NaN handling
   unsigned u = __float_as_uint(f);
   u += 0x7FFFu + ((u >> 16) & 1u);
   return (unsigned short)(u >> 16);
@@ -281,8 +278,8 @@ __device__ __forceinline__ void gemm_tile(const GemmP& p, const int bx, const in
         for (int t = 0; t < TM; ++t)
 #pragma unroll
           for (int i = 0; i < 8; ++i) {
-            a[t][i] = (short)f2bf(As[(ks + khalf * 8 + i) * LD + arow + 32 * t]);
-            b[t][i] = (short)f2bf(Bs[(ks + khalf * 8 + i) * LD + brow + 32 * t]);
+            a[t][i] = (short)f2bf_rne_finite(As[(ks + khalf * 8 + i) * LD + arow + 32 * t]);
+            b[t][i] = (short)f2bf_rne_finite(Bs[(ks + khalf * 8 + i) * LD + brow + 32 * t]);
           }
 #pragma unroll
         for (int i = 0; i < TM; ++i)

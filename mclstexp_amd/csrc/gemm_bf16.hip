@@ -31,41 +31,8 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int BK = 64;
 constexpr int SUB_B = 16384;                  // bytes per 128-row (or 128-column) operand sub-tile
-
-#define MCL_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
-
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(dst)
-               : "memory");
-}
-
-// saddr form: wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset (M0 is used by nothing else here)
-__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0"
-               :
-               : "s"(sbase), "v"(voff), "s"(dst)
-               : "memory", "m0");
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 // ---- k-contiguous tile: [128 rows][64 k] bf16 = 128-byte rows, 16-byte chunk c of row r at physical chunk
 // c ^ ((r >> 1) & 7): 16 consecutive rows of one logical chunk land on 16 distinct 16-byte slots of the 256-byte bank row.

@@ -17,21 +17,12 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
 typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
 constexpr int P = 256;              // embedding width
 constexpr int TC = 128;             // columns per tile
 constexpr int TR = 128;             // rows per workgroup (32 per wave)
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
 
 // exact value of an e4m3 byte
 __device__ __forceinline__ float e4m3_to_f(unsigned v) {

@@ -32,14 +32,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int P = 256;             // embedding width (projection_dim)
 constexpr int TC = 128;           // columns per iteration (rows per workgroup: 32 per wave)
 constexpr int ROWB = P * 2;        // bytes per LDS tile row
@@ -50,15 +42,7 @@ constexpr int STAT_STRIDE = 16384;       // stat tile of buffer b at 2*TILE_B + 
 constexpr int LDS_B = 2 * TILE_B + STAT_STRIDE + STAT_B;
 constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
-#define MCL_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
-#define MCL_GLBP(p) ((const __attribute__((address_space(1))) void*)(p))
-
 __device__ __forceinline__ int fsw(int c) { return ((c & 3) << 2) | ((c >> 2) & 3); }
-
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));  // v_cvt_pk_bf16_f32 (RNE)
-}
 
 // ---- one 128-column tile for one wave (32 rows), as four 32-column blocks and three kinds of work:
 //   A(cb)  16 MFMAs: logits T[c][r] of block cb          (LDS: 16 ds_read_b128, prefetched 4 steps ahead)
@@ -92,30 +76,6 @@ struct Dma {
   int wave_s;                  // wave index, scalar
   const unsigned char* cur;    // scalar: first row of the next piece
 };
-
-__device__ __forceinline__ void glds16(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(dst)
-               : "memory");
-}
-// saddr form: wave-uniform 64-bit base in SGPRs + per-lane 32-bit byte offset
-// (M0 is not saved / restored here: nothing else in these kernels uses it -- checked in the ISA -- and the two extra
-// s_mov per piece are issue slots of a lone wave.)
-__device__ __forceinline__ void glds16s(const void* sbase, unsigned voff, unsigned dst) {
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %0"
-               :
-               : "s"(sbase), "v"(voff), "s"(dst)
-               : "memory", "m0");
-}
-__device__ __forceinline__ void glds4(const void* src, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(dst)
-               : "memory");
-}
 
 // LDS-DMA piece t of this wave: tile rows 2n, 2n+1 with n = wave*ppw + t (1 KiB, lane-linear in LDS).  Lane l lands on
 // row 2n + (l >> 5), physical chunk l & 31, so it FETCHES logical chunk (l & 31) ^ f(row): the swizzle lives in the

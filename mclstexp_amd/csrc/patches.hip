@@ -18,15 +18,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ bf16_t f2bf(float f) {
-  const f32x2 v = {f, 0.0f};
-  return (bf16_t)(__builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t)) & 0xFFFFu);
-}
-
 __global__ __launch_bounds__(256) void patch_gather_kernel(const unsigned char* __restrict__ img, int Hs, int Ws,
                                                            const int* __restrict__ centers, int N, int r,
                                                            const unsigned char* __restrict__ ops, float divisor,

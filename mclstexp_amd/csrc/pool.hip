@@ -6,28 +6,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void unpack8(uint4 v, float (&f)[8]) {
-  const unsigned w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = __uint_as_float(w[i] << 16);
-    f[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  unsigned w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const f32x2 v = {f[2 * i], f[2 * i + 1]};
-    w[i] = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-  }
-  return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
 // y[n, oy, ox, c] = mean of the 2x2 window (H, W even); fp32 accumulation, one rounding
 __global__ __launch_bounds__(256) void avgpool2_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y, int N,
                                                            int H, int W, int C8) {

@@ -27,8 +27,6 @@ constexpr int LDW = 36;          // weight slice row: 32 k + 4 pad
 constexpr int LDT = 260;         // 16 x 256 activation tile row
 constexpr int MAX_KS = 16;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 __device__ __forceinline__ void drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // One BK-slice of a K-contiguous 256-row weight (row stride ld, k in [k0, k0 + 32) clipped to kend) -> 8 float4 per thread.
 // Loads are unconditional, from addresses clamped into the row (a load inside a bounds branch is followed by the compiler's
@@ -134,7 +132,6 @@ constexpr int FWD_LDS_FLOATS = P * LDW + RB * LDW + 2 * RB * LDT + 4;     // wei
 // the weight slices travel through a PD-deep register pipeline (all of a short K slice's loads are in flight at once), the
 // second layer's first PD slices are requested before the partials are read back, and the partials of four K slices at a time.
 constexpr int PD = 4;
-typedef unsigned long long u64;
 
 template <bool VEC>
 __global__ __launch_bounds__(NT) void proj_head_fwd_kernel(const HeadF h) {

@@ -48,10 +48,6 @@ __device__ __forceinline__ float key2f(unsigned k) {
   return __uint_as_float(u);
 }
 
-__device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
-}
-
 // append (key, idx) of the flagged lanes to sel[] through ONE LDS atomic per wave
 __device__ __forceinline__ void wave_append(bool flag, unsigned key, unsigned idx, unsigned long long* sel,
                                             unsigned* counter, unsigned cap) {

@@ -6,15 +6,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
-__device__ __forceinline__ unsigned f2bf_rne(float f) {
-  unsigned u = __float_as_uint(f);
-  if ((u & 0x7F800000u) == 0x7F800000u) return u >> 16;   // inf / nan: truncate
-  u += 0x7FFFu + ((u >> 16) & 1u);
-  return u >> 16;
-}
 __device__ __forceinline__ unsigned pack_rne(float a, float b) { return f2bf_rne(a) | (f2bf_rne(b) << 16); }
 
 // ---------------------------------------------------------------------------------------------------------------------

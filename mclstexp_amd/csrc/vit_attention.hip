@@ -28,15 +28,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef short v4s_t __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
 constexpr int DH = 64;          // head dimension
 
 // 16-byte chunk c of tile row r lives at physical chunk c ^ swz(r): bits 1..3 of r, bit-REVERSED.  Row fragments (ds_read_b128: a
@@ -44,13 +35,6 @@ constexpr int DH = 64;          // head dimension
 // slots; transposing fragments (ds_read_b64_tr_b16: a 32-lane group = 4 consecutive rows x 64 bytes) see rows r, r + 1 on the two
 // 128-byte halves of the bank row and rows r + 2, r + 3 moved by four chunks (bit 1 of r -> chunk bit 2) -> all 64 banks once.
 __device__ __forceinline__ int swz(int row) { return ((row >> 1) & 1) << 2 | ((row >> 2) & 1) << 1 | ((row >> 3) & 1); }
-
-__device__ __forceinline__ unsigned pack2(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ float bf_lo(unsigned w) { return __uint_as_float(w << 16); }
-__device__ __forceinline__ float bf_hi(unsigned w) { return __uint_as_float(w & 0xFFFF0000u); }
 
 // ---- tile fills in two phases so that EVERY global load of a workgroup's prologue is in flight before the first LDS write waits
 // for one: thread t of NT owns the 16-byte chunks t, t + NT, t + 2 NT, t + 3 NT of a [rows][64] source (rows <= NT / 2: a workgroup
@@ -95,15 +79,15 @@ __device__ __forceinline__ bf16x8 frag_tr(const unsigned char* tile, int col0, i
   const int r_lo = row0 + q, r_hi = row0 + 8 + q;
   const unsigned char* p_lo = tile + r_lo * 128 + ((chunk ^ swz(r_lo)) << 4) + (i & 1) * 8;
   const unsigned char* p_hi = tile + r_hi * 128 + ((chunk ^ swz(r_hi)) << 4) + (i & 1) * 8;
-  const v4s_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_t __attribute__((address_space(3)))*)p_lo);
-  const v4s_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s_t __attribute__((address_space(3)))*)p_hi);
+  const v4s lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)p_lo);
+  const v4s hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((v4s __attribute__((address_space(3)))*)p_hi);
   return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
 }
 // registers 8 s2 .. 8 s2 + 7 of a result block, rounded to bf16: the B operand of the next product (slot order = register order)
 __device__ __forceinline__ bf16x8 pack_regs(const f32x16& p, int s2) {
   u32x4 w;
 #pragma unroll
-  for (int e = 0; e < 4; ++e) w[e] = pack2(p[8 * s2 + 2 * e], p[8 * s2 + 2 * e + 1]);
+  for (int e = 0; e < 4; ++e) w[e] = pack_bf16(p[8 * s2 + 2 * e], p[8 * s2 + 2 * e + 1]);
   return __builtin_bit_cast(bf16x8, w);
 }
 // row offset inside a 32-row block of result register r for lane half h
@@ -119,7 +103,7 @@ __device__ __forceinline__ void store_strip(const f32x16 (&acc)[2], unsigned cha
   for (int db = 0; db < 2; ++db)
 #pragma unroll
     for (int g = 0; g < 4; ++g) {          // 4 consecutive d per register group
-      const u32x2 w = {pack2(acc[db][4 * g], acc[db][4 * g + 1]), pack2(acc[db][4 * g + 2], acc[db][4 * g + 3])};
+      const u32x2 w = {pack_bf16(acc[db][4 * g], acc[db][4 * g + 1]), pack_bf16(acc[db][4 * g + 2], acc[db][4 * g + 3])};
       *reinterpret_cast<u32x2*>(st + l31 * 64 + db * 32 + 8 * g + 4 * h) = w;
     }
   // (a wave reads back only what it wrote; LDS operations of a wave complete in order)
@@ -140,7 +124,7 @@ __device__ __forceinline__ void store_strip_halves(const f32x16 (&acc)[2], unsig
   for (int db = 0; db < 2; ++db) {
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-      const u32x2 w = {pack2(acc[db][4 * g], acc[db][4 * g + 1]), pack2(acc[db][4 * g + 2], acc[db][4 * g + 3])};
+      const u32x2 w = {pack_bf16(acc[db][4 * g], acc[db][4 * g + 1]), pack_bf16(acc[db][4 * g + 2], acc[db][4 * g + 3])};
       *reinterpret_cast<u32x2*>(st + l31 * 32 + 8 * g + 4 * h) = w;
     }
 #pragma unroll

@@ -6,17 +6,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((unsigned)v) << 16); }
-__device__ __forceinline__ unsigned pack_bf16(float a, float b) {
-  const f32x2 v = {a, b};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-__device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf16(f, 0.0f) & 0xFFFFu); }
-
 // ---- LayerNorm over D (multiple of 8, <= 1024): one wave per row, 16-byte loads
 constexpr int LN_MAXV = 2;                    // 16-byte chunks per lane (D <= 64 * 8 * 2 = 1024)
 
@@ -297,20 +286,6 @@ __device__ __forceinline__ float half_max(float v) {
 #pragma unroll
   for (int o = 16; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
-}
-__device__ __forceinline__ void unpack8(const uint4 u, float (&v)[8]) {
-  const unsigned w[4] = {u.x, u.y, u.z, u.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    v[2 * i] = __uint_as_float(w[i] << 16);
-    v[2 * i + 1] = __uint_as_float(w[i] & 0xFFFF0000u);
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&v)[8]) {
-  unsigned w[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) w[i] = pack_bf16(v[2 * i], v[2 * i + 1]);
-  return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 __global__ __launch_bounds__(256) void softmax_fwd_vec_kernel(bf16_t* __restrict__ s, long long ld, long long rows, int n) {

@@ -34,11 +34,6 @@
 
 namespace {
 
-typedef unsigned short bf16_t;
-typedef short v4s __attribute__((ext_vector_type(4)));
-typedef short bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int BK = 64;        // pixels per LDS tile
 constexpr int BT = 128;       // channel-tile width of both operands
 constexpr int ROWB = BT * 2;  // bytes per LDS tile row (raw rows as they lie in HBM: 128 bf16)
@@ -53,26 +48,12 @@ constexpr int NSTAGE = 4;
 // bytes, so that the stride is never a power of two (same-offset reads of all slabs would share HBM channels).
 __host__ __device__ inline long long slab_stride(long long MN, int N) { return MN + 2LL * N + 64; }
 
-#define MCL_LDSP(p) ((__attribute__((address_space(3))) void*)(p))
-
-// One LDS-DMA instruction (buffer form): every lane fetches 16 bytes at its own 32-bit byte offset from a per-workgroup
-// descriptor (base = the slab's first row, num_records = the slab's bytes); the wave's 1 KiB lands lane-linear at the
-// (wave-uniform) LDS address in M0 -- no VGPR round trip, no 64-bit address arithmetic per piece.  A 16-byte chunk beyond
-// the slab's end is out of range: it lands in LDS as ZEROS and touches no memory (checked on MI355X), so ragged last
-// tiles and the pipeline's run-out past the last tile need no branch.  Inline asm on purpose: hidden from the compiler's
-// vmcnt bookkeeping, the DMA is covered by the explicit vmcnt(N) + barrier that opens every tile
-// (cdna_hip_programming.md 5.7).
-typedef unsigned u32x4_s __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void blds16(u32x4_s rsrc, unsigned voff, unsigned dst) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(voff), "s"(rsrc), "s"(dst)
-               : "memory");
-}
-__device__ __forceinline__ u32x4_s raw_rsrc(const void* base, unsigned long long bytes) {
+// Descriptor of the per-workgroup slab for buffer_lds16 (base = the slab's first row, num_records = the slab's bytes):
+// ragged last tiles and the pipeline's run-out past the last tile land as zeros and need no branch.  The DMA is covered
+// by the explicit vmcnt(N) + barrier that opens every tile.
+__device__ __forceinline__ u32x4 raw_rsrc(const void* base, unsigned long long bytes) {
   const unsigned long long a = (unsigned long long)base;
-  return u32x4_s{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, (unsigned)(bytes < 0xFFFFFFFFull ? bytes : 0xFFFFFFFFull), 0x00020000u};
+  return u32x4{(unsigned)a, (unsigned)(a >> 32) & 0xFFFFu, (unsigned)(bytes < 0xFFFFFFFFull ? bytes : 0xFFFFFFFFull), 0x00020000u};
 }
 
 // Raw tiles keep 256-byte rows (what the DMA writes), so the transposing reads are de-conflicted by an XOR swizzle
@@ -98,9 +79,6 @@ __device__ __forceinline__ bf16x8 frag_rd(unsigned addr, int kbase) {
   return r;
 }
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef short s16x2_t __attribute__((ext_vector_type(2)));
 
 // Workgroup = 4 waves; wave w owns output columns [32w, 32w + 32) of the 128-column tile and ALL 128 rows (four
@@ -146,8 +124,8 @@ __global__ __launch_bounds__(256, 1) void wrw_partial_kernel(
   // Piece u (u = 0..3) of tile t: tile rows 4p .. 4p+3, p = wave + 4u, of both operands.
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const long long nrow = s_end - s_begin;
-  const u32x4_s rsrc_a = raw_rsrc(dz + s_begin * ldz, nrow > 0 ? (unsigned long long)nrow * ldz * 2 : 0ull);
-  const u32x4_s rsrc_x = raw_rsrc(x + s_begin * ldx, nrow > 0 ? (unsigned long long)((nrow - 1) * ldx + N) * 2 : 0ull);
+  const u32x4 rsrc_a = raw_rsrc(dz + s_begin * ldz, nrow > 0 ? (unsigned long long)nrow * ldz * 2 : 0ull);
+  const u32x4 rsrc_x = raw_rsrc(x + s_begin * ldx, nrow > 0 ? (unsigned long long)((nrow - 1) * ldx + N) * 2 : 0ull);
   unsigned offa[4], offx[4];
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
@@ -158,8 +136,8 @@ __global__ __launch_bounds__(256, 1) void wrw_partial_kernel(
   const unsigned tstep_a = (unsigned)(BK * ldz * 2), tstep_x = (unsigned)(BK * ldx * 2);
   auto dma_piece = [&](int t, int stage, int u) {
     const unsigned dst = lds_base + stage * STAGE_B + (wave_u + 4 * u) * 1024;
-    blds16(rsrc_a, offa[u] + (unsigned)t * tstep_a, dst);
-    blds16(rsrc_x, offx[u] + (unsigned)t * tstep_x, dst + TILE_B);
+    buffer_lds16(rsrc_a, offa[u] + (unsigned)t * tstep_a, dst);
+    buffer_lds16(rsrc_x, offx[u] + (unsigned)t * tstep_x, dst + TILE_B);
   };
   auto dma_tile = [&](int t, int stage) {
 #pragma unroll
