@@ -12,11 +12,17 @@ parameters including both (65536, G) position tables.  Workload = BASELINE.json 
 batch 128 per GPU, 224x224 patches, 1000 genes, bf16 backbone.  N > 1 = data parallel, per-GPU batch
 fixed (weak scaling), global InfoNCE over the all-gathered embeddings.
 
-Prints ONE JSON line (rank 0).  `value` = spots/s of the whole job = steps/s x global batch.
+Prints ONE JSON line (rank 0).  `value` = spots/s of the whole job = steps/s x global batch.  A plain run does only
+what that figure needs: set-up, the W warm-up steps, the K timed steps, the dump below if asked for, the line.
+
+`--full` adds, after the timed region, what the headline does not need:
 `roofline` = the C-ABI launch unit with the LARGEST time per step (`roofline_kernels` lists the others), each
 call timed with HIP events on its launch stream in an eager pass right after the timed region (same process, same
-resident model and inputs; every kernel alone on the GPU: side streams off).  `cpu_baseline` = the CPU oracle
+resident model and inputs; every kernel alone on the GPU: side streams off), with the step's kernel audit
+(`config.step_kernel_audit`).  `config.position_tables` = the cost of materialising the lazy position tables.
+`config.parity_at_benched_shape` = the parity figures the GPU tests recorded.  `cpu_baseline` = the CPU oracle
 (oracle/ref_cpu.py) timed on this host's cores on the same workload, a bounded number of steps (N=1 only).
+`--no_cpu_baseline` and `--profile_steps 0` leave parts of that out.
 
 `--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (``dump_outputs``).  The inputs and the
 model's initial state are seeded, so two builds run with the same arguments can be compared array for array.
@@ -61,13 +67,16 @@ def parse():
                     help="fused = flash-style bf16 MFMA InfoNCE (logits never in HBM); exact = fp32 GEMM + LSE kernels; "
                          "fp8 = the fused kernel on e4m3 operands (BASELINE configs[4])")
     ap.add_argument("--backbone_dtype", type=str, default="bf16", choices=["bf16", "f32"])
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also time the kernels one by one (`roofline`, kernel audit), the position "
+                         "tables' materialisation and the CPU oracle (`cpu_baseline`), and relay the recorded parity figures")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: no `cpu_baseline`")
     ap.add_argument("--no_graphs", action="store_true", help="A/B: eager launches instead of HIP-graph replay")
     ap.add_argument("--unfused_backbone", action="store_true", help="A/B: plain torch module path for the backbone")
     ap.add_argument("--cpu_budget_s", type=float, default=25.0)
     ap.add_argument("--profile_steps", type=int, default=2,
-                    help="eager steps after the timed region in which the hot C-ABI calls are timed with HIP events "
-                         "(0 = no `roofline` object)")
+                    help="with --full: eager steps after the timed region in which the hot C-ABI calls are timed with HIP "
+                         "events (0 = no `roofline` object)")
     ap.add_argument("--dense_tables", action="store_true",
                     help="A/B: update every row of the two position tables on every step (1.57 GB of state traffic) instead of "
                          "the lazy-exact form (optim.FusedAdam(lazy_tables=True): untouched rows are replayed on demand)")
@@ -130,7 +139,7 @@ def _cpu_baseline_worker(genes: int, image: int, batch: int, budget_s: float) ->
 
 def cpu_baseline(args, budget_s: float):
     """Oracle (a port: the reference cannot run unmodified on CPU) timed on the host cores in a
-    child process with a hard wall-clock limit, so the default bench always finishes."""
+    child process with a hard wall-clock limit, so a --full run always finishes."""
     import subprocess
     code = ("import json,sys; sys.path.insert(0, %r); import bench; "
             "print('CPUBASE ' + json.dumps(bench._cpu_baseline_worker(%d, %d, %d, %f)))"
@@ -430,23 +439,27 @@ def main():
         dt = float(t.item())
 
     # Lazy-exact position tables: the rows no batch touched are advanced when the table is materialised (state_dict /
-    # checkpoint).  That work is deferred, not skipped -- time a full materialisation now (every row replays all the steps
-    # of this run) and report it separately and amortised over the steps it covers.
+    # checkpoint).  That work is deferred, not skipped -- with --full, time a full materialisation now (every row replays all
+    # the steps of this run) and report it separately and amortised over the steps it covers.  The dump below holds the
+    # materialised tables, so --dump-outputs materialises them too.
     tables_info = {"mode": "dense: every row of both tables on every step"}
     if opt.lazy_tables and opt._tables:
-        behind = opt._step_count - opt._lazy_flushed_at
-        torch.cuda.synchronize()
-        tm0 = time.perf_counter()
-        opt.materialize_tables()
-        torch.cuda.synchronize()
-        mat_ms = 1e3 * (time.perf_counter() - tm0)
         tables_info = {"mode": "lazy-exact (optim.FusedAdam(lazy_tables=True)): rows a batch gathers / updates are replayed to "
                                "the current step in registers, bit-identical to the dense per-step update "
-                               "(tests/test_lazy_tables_gpu.py); all other rows when the table is materialised",
-                       "full_materialize_ms": round(mat_ms, 3), "steps_replayed_per_row": behind,
-                       "amortized_ms_per_step": round(mat_ms / max(1, behind), 5),
-                       "note": "NOT inside the timed region: a checkpoint (model.state_dict()) pays full_materialize_ms once; "
-                               "ms_per_step + amortized_ms_per_step is the all-inclusive figure"}
+                               "(tests/test_lazy_tables_gpu.py); all other rows when the table is materialised"}
+        if args.full or args.dump_outputs:
+            behind = opt._step_count - opt._lazy_flushed_at
+            torch.cuda.synchronize()
+            tm0 = time.perf_counter()
+            opt.materialize_tables()
+            torch.cuda.synchronize()
+            mat_ms = 1e3 * (time.perf_counter() - tm0)
+            if args.full:
+                tables_info.update({"full_materialize_ms": round(mat_ms, 3), "steps_replayed_per_row": behind,
+                                    "amortized_ms_per_step": round(mat_ms / max(1, behind), 5),
+                                    "note": "NOT inside the timed region: a checkpoint (model.state_dict()) pays "
+                                            "full_materialize_ms once; ms_per_step + amortized_ms_per_step is the all-inclusive "
+                                            "figure"})
 
     dumped = None
     if args.dump_outputs and rank == 0:
@@ -457,7 +470,7 @@ def main():
     # collectives of the other ranks are not left waiting)
     roof_rows = []
     foreign_kernels = None
-    if args.profile_steps > 0 and world == 1 and args.encoder == "densenet121" and not args.unfused_backbone:
+    if args.full and args.profile_steps > 0 and world == 1 and args.encoder == "densenet121" and not args.unfused_backbone:
         log(f"kernel timing pass: {args.profile_steps} eager steps, HIP events per C-ABI call")
         eager = TrainStep(model, opt, reducer, graphs=False)
         if getattr(model, "embedding_grad", "dense") == "rowsparse":
@@ -502,7 +515,7 @@ def main():
                        "dp_backward_segments": (len(trainer.seg_graphs) + 1 if (dist_on and trainer.seg_graphs) else None),
                        "fallbacks": densenet_fused.fallback_counts(),
                        "step_kernel_audit": foreign_kernels,
-                       "parity_at_benched_shape": parity_artifact(args),
+                       "parity_at_benched_shape": parity_artifact(args) if args.full else None,
                        "final_loss": round(final_loss, 4),
                        "final_loss_note": f"{args.n_batches} synthetic batches are cycled: the loss reflects "
                                           "memorisation of that set, it is not a convergence claim"},
@@ -520,7 +533,7 @@ def main():
         }
         if dumped is not None:
             out["outputs_dump"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("gpu done: %.2f ms/step; timing the CPU oracle baseline" % out["ms_per_step"])
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_budget_s)
         sys.stdout.flush()
