@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCL_ABI_VERSION 11
+#define MCL_ABI_VERSION 12
 
 #define MCL_OK 0
 #define MCL_EINVAL (-1)       /* null pointer / non-positive size / inconsistent arguments */
@@ -811,6 +811,54 @@ int mcl_knn_weighted_average(const float* spot_key, int64_t ldk, const float* ex
 int mcl_expr_metrics(const void* pred, int64_t ld_pred, int32_t pred_dtype, const void* truth, int64_t ld_true,
                      int32_t true_dtype, const int64_t* offsets, int32_t S, int32_t G, int32_t n_heg, double* r,
                      double* true_mean, int64_t* heg, double* summary, double* work, mcl_stream_t stream);
+
+/* ---------------------------------------------------------------- spatial-domain clustering (ABI 12; csrc/cluster.hip)
+ * The reference's cluster() (utils.py:67-79): PCA -> k-means -> ARI / NMI against given labels, for S slides per call.
+ * Common contract: row-stacked row-major device matrices, offsets[S + 1] device-resident int64 with offsets[0] = 0, every
+ * segment non-empty; S <= 65535; all results fp64; floating-point sums are atomics-free and their order depends only on
+ * the segment's own shape: a segment computed inside a batch is bit-identical to the same segment computed alone.
+ *
+ * mcl_pca_gram: x (rows, G), leading dimension ld >= G, dtype 0 = float32 / 1 = float64.  Per segment s of n_s rows:
+ *   mean[s * G + g] = the column means, and at gram[gram_offsets[s]] the centred Gram matrix in its smaller form, row-major
+ *   m_s x m_s with m_s = min(n_s, G): Xc^T Xc when n_s >= G ("primal"), else Xc Xc^T ("dual"); fp64 accumulation on
+ *   v_mfma_f64_16x16x4_f64 in index order; full matrix, exactly symmetric.  gram_offsets[S + 1] (device int64) are element
+ *   offsets, gram_offsets[s + 1] - gram_offsets[s] >= m_s^2.  max_rows = the largest n_s (sizes the grid).
+ * mcl_pca_project: the top n_comps <= 64 eigenpairs of that matrix, found on the host: evec at evec_offsets[s] (device int64
+ *   element offsets) row-major (m_s, n_comps), eval[s * n_comps + c] the eigenvalues, best first.  Writes the scores
+ *   z (rows, n_comps): primal Xc V, dual U sqrt(lambda) -- sklearn's PCA.fit_transform -- with each component's sign chosen
+ *   so that its loading of largest magnitude (ties: the lowest column) is positive (sklearn >= 1.5's svd_flip on V);
+ *   sign[s * n_comps + c] = +-1 is that factor; loadings: S * G * n_comps doubles of scratch.  n_s >= G decides primal / dual
+ *   exactly as in mcl_pca_gram.
+ * mcl_kmeans: z (rows, D) fp64, leading dimension ld; k[s] (device int32) clusters in segment s, 1 <= k[s] <= min(k_max, n_s)
+ *   (otherwise that segment reports inertia NaN, n_iter -1, labels -1); D <= 64 and k_max <= 64, MCL_EUNSUPPORTED beyond.
+ *   Grid (restart r < R, segment s): one workgroup runs one whole Lloyd problem in one launch.  Seeding: seeds != NULL:
+ *   seeds[(s * R + r) * k_max + j] (device int64) is the row, inside the segment, of initial centre j; seeds == NULL:
+ *   k-means++ with one candidate per centre (first centre uniform, then D^2 sampling through a fixed-order prefix sum) from
+ *   a counter-based generator keyed by (seed, segment_base + s, r, draw) -- NOT NumPy's stream.  seeds_out gets the rows
+ *   used, same layout.  Iteration = sklearn's algorithm="lloyd": nearest centre by squared Euclidean distance (ties: lowest
+ *   centre), means; an emptied cluster takes the point farthest from its own centre (ties: lowest row); stop when no label
+ *   changed, or when sum ||c_new - c_old||^2 <= tol * mean_d var(z[:, d]), or after max_iter iterations; then one final
+ *   assignment unless the labels were already stable; inertia from the final labels and centres.
+ *   Per restart: labels_all (R, rows) int32, centers_all (S, R, k_max, D), inertia_all (S, R), n_iter_all (S, R) int32;
+ *   work: R * rows doubles of scratch.  A second launch picks per segment the restart of lowest inertia (ties: lowest r):
+ *   labels (rows) int32, centers (S, k_max, D), inertia (S), n_iter (S) int32, restart (S) int32.
+ * mcl_cluster_scores: labels_a ("true") and labels_b (rows) int32, values in [0, 1024), distinct(a) * distinct(b) <= 12288
+ *   per segment (else that segment scores NaN); max_rows = the largest n_s <= 50000 (pair counts stay inside int64),
+ *   MCL_EUNSUPPORTED beyond.  scores[2 s] = adjusted Rand index in sklearn's pair-confusion form (1.0 when fn = fp = 0),
+ *   scores[2 s + 1] = normalized mutual information, average_method="arithmetic", natural log (1.0 when both labellings
+ *   have one class, 0.0 when only one has, MI clamped at 0).  Contingency table in LDS by integer atomics.             */
+int mcl_pca_gram(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int32_t G, int32_t max_rows,
+                 const int64_t* gram_offsets, double* mean, double* gram, mcl_stream_t stream);
+int mcl_pca_project(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int32_t G,
+                    int32_t max_rows, int32_t n_comps, const double* mean, const double* evec, const int64_t* evec_offsets,
+                    const double* eval, double* loadings, double* sign, double* z, mcl_stream_t stream);
+int mcl_kmeans(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D, const int32_t* k,
+               int32_t k_max, int32_t R, const int64_t* seeds, uint64_t seed, int32_t segment_base, double tol,
+               int32_t max_iter, int64_t* seeds_out, int32_t* labels_all, double* centers_all, double* inertia_all,
+               int32_t* n_iter_all, double* work, int32_t* labels, double* centers, double* inertia, int32_t* n_iter,
+               int32_t* restart, mcl_stream_t stream);
+int mcl_cluster_scores(const int32_t* labels_a, const int32_t* labels_b, const int64_t* offsets, int32_t S,
+                       int32_t max_rows, double* scores, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;

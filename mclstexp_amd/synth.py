@@ -167,3 +167,24 @@ def make_eval_case(segments: Sequence[int], genes: int, seed: int = 0, const_tru
         true[:, genes - 1] = 2.0 * float(true.mean(axis=0).max()) + 1.0
     offsets = np.concatenate([[0], np.cumsum(np.asarray(segments, dtype=np.int64))]).astype(np.int64)
     return {"pred": np.ascontiguousarray(pred), "true": np.ascontiguousarray(true), "offsets": offsets}
+
+
+def make_cluster_case(n: int, genes: int, k: int, seed: int = 0, sep: float = 0.1,
+                      undetermined_frac: float = 0.1) -> Dict[str, np.ndarray]:
+    """Synthetic spatial-domain clustering problem for ``mclstexp_amd.cluster``: ``k`` latent cluster programmes (12
+    factors, scale ``sep``) times random gene loadings plus unit noise on a per-gene baseline, ``log1p`` of the positive
+    part -- ``pred`` (n, genes) float64, shaped like a predicted log-expression matrix.  ``label`` (n,) holds the
+    cluster of every spot as a string ('0' .. str(k - 1)) with a fraction ``undetermined_frac`` replaced by
+    'undetermined' (the annotation the reference's cluster() drops); ``truth`` (n,) int64 is the cluster of every spot.
+    Drawn from ``numpy.random.default_rng(seed)`` (unlike the hash-generated tensors above: the draws are normal)."""
+    r = np.random.default_rng(seed)
+    truth = r.integers(0, k, n)
+    prog = r.standard_normal((k, 12)) * sep
+    load = r.standard_normal((12, genes))
+    base = np.abs(r.standard_normal(genes)) * 2
+    x = base + prog[truth] @ load * 0.5 + r.standard_normal((n, genes)) * 1.0
+    x = np.log1p(np.maximum(x, 0))
+    und = r.random(n) < undetermined_frac
+    label = truth.astype(str).astype(object)
+    label[und] = "undetermined"
+    return {"pred": np.ascontiguousarray(x), "label": label.astype(str), "truth": truth.astype(np.int64)}
