@@ -24,7 +24,7 @@
 extern "C" {
 #endif
 
-#define MCL_ABI_VERSION 12
+#define MCL_ABI_VERSION 13
 
 #define MCL_OK 0
 #define MCL_EINVAL (-1)       /* null pointer / non-positive size / inconsistent arguments */
@@ -859,6 +859,49 @@ int mcl_kmeans(const double* z, int64_t ld, const int64_t* offsets, int32_t S, i
                int32_t* restart, mcl_stream_t stream);
 int mcl_cluster_scores(const int32_t* labels_a, const int32_t* labels_b, const int64_t* offsets, int32_t S,
                        int32_t max_rows, double* scores, mcl_stream_t stream);
+
+/* ---------------------------------------------------------------- count tables -> HVGs -> expression matrices (ABI 13;
+ * csrc/preprocess.hip).  The reference's hvg_her2st.py / hvg_cscc.py / hvg_visium.py for S slides per call.
+ * Slide set (all five arrays DEVICE-resident, the caller checks them; the library cannot before launching): slides[s] the
+ *   row-major (rows[s], ncols[s]) count matrix of slide s, leading dimension ld[s] >= ncols[s] (elements), every slide of the
+ *   one dtype (0 = float32, 1 = int32); row_offsets[S + 1] int64 = the running sum of rows (row_offsets[0] = 0).
+ *   2 <= rows[s] <= 50000 = max_rows' bound, S <= 65535, 2 <= G <= 1048576 (MCL_EUNSUPPORTED beyond).
+ * mcl_hvg_stats: colmaps NULL (gene g is column g of every slide, ncols[s] >= G) or (S, G) int32, colmaps[s * G + g] = the
+ *   column of shared gene g in slide s (an entry outside [0, ncols[s]) is read as the nearest valid column and reported).
+ *   Per slide, what scanpy computes for normalize_total(target_sum=None), log1p, highly_variable_genes(flavor="seurat",
+ *   n_bins=20, n_top_genes), all fp64, the fp32 log1p / expm1 round trip left out:
+ *     target_sum[s]                 the median of the positive library sizes s_i = sum_g c_ig (NaN if there is none);
+ *     x_ig = c_ig / f_i             f_i = s_i / target_sum, 1 where that is 0;
+ *     means[s * G + g]              log1p(mean), mean = sum_i x_ig / n with an exact 0 replaced by 1e-12;
+ *     dispersions[s * G + g]        log(var / mean), var = (E[x^2] - mean^2) n / (n - 1), a ratio of exactly 0 -> NaN;
+ *     mean_bin[s * G + g]           0 .. 19: pandas.cut(means, 20) (numpy.linspace edges, the lowest lowered by 0.1 % of the
+ *                                   range, intervals closed on the right);
+ *     dispersions_norm[s * G + g]   (dispersions - bin mean) / bin std (ddof = 1) over the bin's non-NaN dispersions; a bin
+ *                                   with fewer than two of them takes std = its mean and mean = 0; IEEE results for std = 0;
+ *     cutoff[s]                     the min(n_top_genes, number of non-NaN)-th largest non-NaN dispersions_norm;
+ *     highly_variable[s * G + g]    1 where nan_to_num(dispersions_norm) >= cutoff, else 0 (ties all pass; NaN genes pass
+ *                                   when cutoff <= 0, as in scanpy);
+ *     status[s]                     0, or bits: 1 the means are all equal or not finite (outputs: NaN / 0; pandas' widening
+ *                                   of a flat range is not reproduced), 2 no positive library size, 4 no non-NaN
+ *                                   dispersions_norm, 8 a column map entry out of range.
+ *   work: row_offsets[S] doubles (the size factors).  Four launches, no floating-point atomics, every summation order a
+ *   function of (rows[s], G) alone: a slide inside a batch is bit-identical to the slide alone, run to run.
+ * mcl_hvg_pool: highly_variable (S, G) -> union_out / intersection_out (G) bytes, then union_out[extra[j]] = 1 for the
+ *   n_extra int32 gene indices (hvg_her2st.py:64; indices outside [0, G) are ignored).
+ * mcl_expression_matrices: sel (S, K) int32 = the columns of slide s to keep, in output order.  For slide s writes at
+ *   out + K * row_offsets[s] the (K, rows[s]) row-major fp32 matrix log10(c / rowsum * rescale + 1), rowsum over the K kept
+ *   columns only -- scprep.transform.log(scprep.normalize.library_size_normalize(.)) of the subset, transposed into the
+ *   layout of preprocessed_matrix.npy; an all-zero spot stays zero as in mcl_log_library_size_normalize.  K <= 1048576. */
+int mcl_hvg_stats(const void* const* slides, const int64_t* ld, const int32_t* rows, const int32_t* ncols,
+                  const int64_t* row_offsets, int32_t dtype, const int32_t* colmaps, int32_t S, int32_t G,
+                  int32_t max_rows, int32_t n_top_genes, double* work, double* means, double* dispersions,
+                  double* dispersions_norm, int32_t* mean_bin, uint8_t* highly_variable, double* cutoff,
+                  double* target_sum, int32_t* status, mcl_stream_t stream);
+int mcl_hvg_pool(const uint8_t* highly_variable, int32_t S, int32_t G, const int32_t* extra, int32_t n_extra,
+                 uint8_t* union_out, uint8_t* intersection_out, mcl_stream_t stream);
+int mcl_expression_matrices(const void* const* slides, const int64_t* ld, const int32_t* rows, const int32_t* ncols,
+                            const int64_t* row_offsets, int32_t dtype, const int32_t* sel, int32_t S, int32_t K,
+                            int32_t max_rows, float rescale, float* out, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;

@@ -17,7 +17,7 @@ import torch  # noqa: F401  (side effect: loads torch/lib/libamdhip64.so)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MCL_LIB_PATH") or os.path.join(_HERE, "libmclstexp_hip.so")   # override: A/B of kernel builds
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _lib: Optional[C.CDLL] = None
 
@@ -217,6 +217,9 @@ PROTOTYPES = {
     "mcl_kmeans": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, C.c_uint64, c_i, c_d, c_i, c_p, c_p, c_p, c_p, c_p, c_p,
                    c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_cluster_scores": [c_p, c_p, c_p, c_i, c_i, c_p, c_p],
+    "mcl_hvg_stats": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_hvg_pool": [c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p],
+    "mcl_expression_matrices": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_f, c_p, c_p],
 }
 _RESTYPES = {"mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32, "mcl_gemm_args_min_size": C.c_uint32, "mcl_dense_block_fwd_workspace_bytes": C.c_int64, "mcl_dense_block_bwd_workspace_bytes": C.c_int64, "mcl_bn_workspace_floats": C.c_int64,
              "mcl_infonce_fused_workspace_bytes": C.c_int64, "mcl_dense_conv1x1_workspace_floats": C.c_int64,

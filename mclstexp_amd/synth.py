@@ -188,3 +188,44 @@ def make_cluster_case(n: int, genes: int, k: int, seed: int = 0, sep: float = 0.
     label = truth.astype(str).astype(object)
     label[und] = "undetermined"
     return {"pred": np.ascontiguousarray(x), "label": label.astype(str), "truth": truth.astype(np.int64)}
+
+
+def make_counts_case(spots: int, genes: int, seed: int = 0, zero_genes: int = 0, zero_spot: bool = False,
+                     top_gene: bool = False, duplicate: Optional[Tuple[int, int]] = None,
+                     dtype=np.int32) -> Dict[str, np.ndarray]:
+    """Synthetic raw count table for ``mclstexp_amd.preprocess``: ``counts`` (spots, genes), negative-binomial with mean
+    ``depth_i * mean_g`` and dispersion ``disp_g`` (variance = mu + disp * mu^2).  ``mean`` (log-uniform over
+    exp(-4) .. exp(2.5)), ``disp`` (0.1 .. 2) and ``depth`` (0.5 .. 2) come from the counter-based generator above, and so
+    does the uniform draw behind every count (inverse CDF by the pmf recursion in fp64): no NumPy random stream.
+    ``zero_genes``: that many evenly spread all-zero columns; ``zero_spot``: spot 1 holds no count; ``top_gene``: the last
+    gene gets 40 x the largest mean, alone in the top mean bin; ``duplicate`` = (a, b): column b is a copy of column a."""
+    tag = f"counts.{spots}x{genes}"
+    mean = np.exp(uniform_tensor(tag + ".mean", (genes,), -4.0, 2.5, seed).numpy().astype(np.float64))
+    disp = uniform_tensor(tag + ".disp", (genes,), 0.1, 2.0, seed).numpy().astype(np.float64)
+    depth = uniform_tensor(tag + ".depth", (spots,), 0.5, 2.0, seed).numpy().astype(np.float64)
+    if top_gene:
+        mean[genes - 1] = 40.0 * mean[:genes - 1].max()
+        disp[genes - 1] = 0.5
+    u = uniform_tensor(tag + ".u", (spots, genes), 0.0, 1.0, seed).numpy().astype(np.float64).reshape(-1)
+    mu = (depth[:, None] * mean[None, :]).reshape(-1)
+    r = np.broadcast_to(1.0 / disp[None, :], (spots, genes)).reshape(-1)
+    q = mu / (r + mu)
+    pmf = np.exp(r * np.log1p(-q))                       # P(0) = (r / (r + mu))^r
+    cdf = pmf.copy()
+    k = np.zeros(u.shape, dtype=np.int64)
+    live = np.flatnonzero(u >= cdf)
+    step = 0
+    while live.size and step < 100000:                   # P(k + 1) = P(k) (k + r) / (k + 1) q
+        pmf[live] *= (step + r[live]) / (step + 1.0) * q[live]
+        cdf[live] += pmf[live]
+        k[live] += 1
+        step += 1
+        live = live[(u[live] >= cdf[live]) & (pmf[live] > 0.0)]
+    counts = k.reshape(spots, genes)
+    if zero_genes:
+        counts[:, (np.arange(zero_genes) * genes) // zero_genes + genes // (2 * zero_genes)] = 0
+    if duplicate is not None:
+        counts[:, duplicate[1]] = counts[:, duplicate[0]]
+    if zero_spot:
+        counts[1, :] = 0
+    return {"counts": np.ascontiguousarray(counts.astype(dtype)), "mean": mean, "disp": disp, "depth": depth}
