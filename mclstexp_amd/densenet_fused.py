@@ -27,7 +27,7 @@ from __future__ import annotations
 
 import contextlib
 import os
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -203,6 +203,13 @@ def _direct_grad_ok(p: Tensor) -> bool:
     return True
 
 
+def _direct_all(*params: Tensor) -> bool:
+    """Do ALL of these parameters take the direct path?  ``DIRECT_PARAM_GRADS`` is tested here because ``_direct_grad_possible``
+    ignores it once a .grad exists.  The parameters are tested in the given order and the test stops at the first failure
+    (``_direct_grad_ok`` creates a missing .grad: a parameter behind a failing one gets none)."""
+    return DIRECT_PARAM_GRADS and all(_direct_grad_ok(p) for p in params)
+
+
 def bn_act_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, rstd: Tensor, relu: bool,
                dx: Tensor, accumulate: bool, into_param_grads: bool = False
                ) -> Tuple[Optional[Tensor], Optional[Tensor]]:
@@ -251,7 +258,7 @@ class BNActFn(torch.autograd.Function):
         gamma, beta = ctx.params
         dy = dense_cl(dy)
         dx = torch.empty_like(x, memory_format=CL)
-        direct = DIRECT_PARAM_GRADS and _direct_grad_ok(gamma) and _direct_grad_ok(beta)
+        direct = _direct_all(gamma, beta)
         dg, db = bn_act_bwd(dy, x, gamma, beta, mean, rstd, ctx.relu, dx, False, into_param_grads=direct)
         return dx, dg, db, None, None, None
 
@@ -419,12 +426,11 @@ BN1_SINGLE_PASS_MAX_MAP = 256
 # throughput-bound, the side work costs its full duration anyway, and saving one pass over (dz, x) per layer wins:
 # fused from 200 000 pixels up 14.08 / 14.12 ms/step, from 50 000 up 14.15, never 14.28 / 14.36 (interleaved A/B); after the
 # side-lane grids were shrunk (csrc/wrw_fused.hip plan()): from 50 000 up 13.59 / 13.60, from 200 000 up 13.70 / 13.76.
-USE_FUSED_BN1_WRW = True
 FUSED_BN1_WRW_MIN_PIXELS = 50000
 
 
 def _bn1_wrw_ok(w_param: Tensor) -> bool:
-    return (USE_FUSED_BN1_WRW and DIRECT_PARAM_GRADS and _direct_grad_ok(w_param) and w_param.grad.is_contiguous()
+    return (_direct_all(w_param) and w_param.grad.is_contiguous()
             and w_param.shape[0] == 128 and w_param.shape[2:] == (1, 1))
 
 
@@ -479,34 +485,11 @@ def dense_bn1_dx_pair(A, B, x: Tensor, mean: Tensor, rstd: Tensor, gbuf: Tensor)
                                            mean.data_ptr(), rstd.data_ptr(), pg, ldg, _stream()), "mcl_dense_bn1_dx_pair")
 
 
-def dense_bn1_wrw_dx(dz: Tensor, w16: Tensor, x: Tensor, g1: Tensor, b1: Tensor, mean: Tensor, rstd: Tensor, gbuf: Tensor,
-                     w_param: Tensor, into_param_grads: bool) -> Tuple[Optional[Tensor], Optional[Tensor]]:
-    """w_param.grad += dz^T relu(bn1(x)); norm1 parameter gradients; gbuf += d loss / d x -- two C-ABI calls
-    (mcl_dense_bn1_wrw: Gram partials + fixed-order merge; mcl_dense_bn1_dx)."""
-    dg, db, coef = dense_bn1_wrw(dz, w16, x, g1, b1, mean, rstd, w_param, into_param_grads)
-    dense_bn1_dx(dz, w16, x, g1, b1, mean, rstd, coef, gbuf)
-    return dg, db
-
-
-# Round 6: the dx passes of two consecutive layers of a 56 x 56 / 28 x 28 block as ONE pass over the channels both read (x and
-# the gradient buffer read once, the buffer written once; layer l's term on the 32 channels layer l - 1 produced goes first, in a
-# windowed launch).  MCL_BN1_PAIR=0: one dx pass per layer (A/B).
-USE_BN1_PAIR = os.environ.get("MCL_BN1_PAIR", "1") != "0"
-
-
 # conv2 (3x3) backward-data + norm2/relu2 backward (csrc/dense_bwd.hip): dy is read in place from the gradient buffer
-
-
-# The 32-channel mean-term correction of the single-pass BatchNorm-1 backward (mcl_dense_bn1_fix: a 5 us launch in front of
-# every 3x3 backward-data kernel of the 14 x 14 / 7 x 7 blocks, 38 per step on the critical chain) folded into that kernel's
-# dy staging (DESIGN 4.0e).  MCL_FOLD_BN1_FIX=0: the separate launch (A/B; bit-identical results).
-FOLD_BN1_FIX = True
 
 
 def _c3_flat_kernel(W: int) -> bool:
     """True when the 3x3 backward-data of a W-wide map runs the flat-tile kernel (csrc/dense_bwd.hip bwd_rows_applicable)."""
-    if False:
-        return True
     return W < 17 or W > 150
 
 
@@ -601,7 +584,7 @@ def dense_conv3x3_wrw(dy: Tensor, z: Tensor, g2: Tensor, b2: Tensor, m2: Tensor,
 
 def _wrw3_direct_ok(w_param: Tensor, z: Tensor, dy: Tensor) -> bool:
     """dense_conv3x3_wrw's precondition (it accumulates into w_param.grad)."""
-    return (DIRECT_PARAM_GRADS and _direct_grad_ok(w_param) and tuple(w_param.shape) == (32, 128, 3, 3)
+    return (_direct_all(w_param) and tuple(w_param.shape) == (32, 128, 3, 3)
             and dy.dtype == torch.bfloat16 and z.dtype == torch.bfloat16 and z.is_contiguous(memory_format=CL))
 
 
@@ -624,7 +607,7 @@ def conv1x1_wrw(dz: Tensor, a: Tensor, w_param: Tensor, bn=None) -> Optional[Ten
     pz, S, M, ldz = _rows(dz)
     pa, S2, N, lda = _rows(a)
     assert S == S2 and dz.dtype == a.dtype == torch.bfloat16
-    if DIRECT_PARAM_GRADS and _direct_grad_ok(w_param) and w_param.grad.is_contiguous():
+    if _direct_all(w_param) and w_param.grad.is_contiguous():
         tgt, ret = w_param.grad, None
     else:
         tgt = torch.zeros((M, N, 1, 1), device=dz.device, dtype=torch.float32)
@@ -655,7 +638,7 @@ def _same_order(a: Tensor, b: Tensor) -> bool:
 def _wgrad(w: Tensor, dw: Tensor) -> Optional[Tensor]:
     """Weight gradient hand-over: add into an existing dense fp32 .grad (one mixed-dtype add kernel) or
     return it to autograd in the parameter's dtype."""
-    if DIRECT_PARAM_GRADS and _direct_grad_ok(w) and _same_order(dw, w.grad) and dw.dtype in (
+    if _direct_all(w) and _same_order(dw, w.grad) and dw.dtype in (
             torch.bfloat16, torch.float32):
         # (a mixed-dtype torch add_ on the channels-last strided view costs 45 us per weight)
         check(_lib.lib().mcl_accum_into_f32(w.grad.data_ptr(), dw.data_ptr(), dw.numel(), _dt(dw), _stream()),
@@ -718,68 +701,90 @@ def _conv_bwd(dy: Tensor, x: Tensor, w: Tensor, w_param: Tensor, padding: int, c
     return dx, dw
 
 
-# The two weight-gradient kernels of a layer are independent of its data-gradient chain (they only add into .grad):
-# issue them on a side stream so they overlap the latency-bound backward-data / BatchNorm-backward launches (under
-# HIP-graph capture this becomes a parallel branch of the graph).  Joined at the end of every layer.
+# The weight-gradient kernels of a layer are independent of its data-gradient chain (they only add into .grad): issue them
+# on a side stream so they overlap the latency-bound backward-data / BatchNorm-backward launches (under HIP-graph capture
+# this becomes a parallel branch of the graph).
+#
+# Every cross-stream edge of the captured graph costs the WAITING stream ~16 us (tools/trace_gaps.py), so the main chain
+# never waits per kernel: side work is forked off behind an event (``_side_fork``), the tensors it reads are parked (so that
+# the allocator cannot hand their memory out again), and the main stream joins once per dense block / at the stem.
+#
+# Side work whose only dependency is "everything the main stream has issued so far" can be DEFERRED to the next fork the
+# backward makes anyway.  The persistent dense-block backward is ONE kernel followed by 32 weight-gradient launches: forking
+# the side stream right behind that kernel (one cross-stream edge out of a 0.9 ms node) made the replayed step graph lose its
+# two-lane execution -- the spot branch's backward, which precedes those launches on the side stream, then ran 4.5 ms late
+# (profiles/r05_persistent_bwd_lanes.txt).  Riding on the next block's first per-layer fork keeps the graph's edge structure
+# what it was.
 USE_SIDE_STREAM = True             # (bench.py switches it off for its per-kernel timing pass)
-_side_streams = {}
-
-
-def _side_stream(device) -> torch.cuda.Stream:
-    s = _side_streams.get(device.index)
-    if s is None:
-        s = torch.cuda.Stream(device=device)
-        _side_streams[device.index] = s
-    return s
-
-
-# Deferred joins of the side stream.  Every cross-stream edge of the captured graph costs the WAITING stream ~16 us
-# (tools/trace_gaps.py), so the main chain never waits per kernel: side work is forked off with an event, the tensors
-# it reads are parked here (so that the allocator cannot hand their memory out again), and the main stream joins
-# once per dense block / at the stem.
-_side_parked: dict = {}
 JOIN_MIN_PIXELS = 300000
 
 
+class _Side:
+    """One device's side stream, the tensors parked for it and the jobs deferred to its next fork."""
+
+    def __init__(self, device):
+        self.stream = torch.cuda.Stream(device=device)
+        self.parked: list = []
+        self.pending: list = []
+
+
+_sides: dict = {}
+
+
+def _side(device) -> _Side:
+    s = _sides.get(device.index)
+    if s is None:
+        s = _sides[device.index] = _Side(device)
+    return s
+
+
+def _side_stream(device) -> torch.cuda.Stream:
+    return _side(device).stream
+
+
 def _side_park(device, *tensors) -> None:
-    _side_parked.setdefault(device.index, []).extend(tensors)
+    _side(device).parked.extend(tensors)
+
+
+def _fork_event(device) -> torch.cuda.Event:
+    """Everything the current stream has issued so far."""
+    ev = torch.cuda.Event()
+    ev.record(torch.cuda.current_stream(device))
+    return ev
+
+
+def _side_fork(device, job, operands=(), lanes: bool = True, event: Optional[torch.cuda.Event] = None, defer: bool = False):
+    """Runs ``job`` (weight gradients: launches that only add into .grad or return fresh tensors) off the main chain and
+    returns its result.  The side stream waits for ``event`` (default: what the current stream has issued so far), runs the
+    jobs deferred earlier and then ``job``; ``operands``, the tensors the job reads, stay parked until the next join.
+    ``defer``: the job only joins the deferred ones (it returns nothing).  ``lanes = False``: the job runs here and now."""
+    if not lanes:
+        return job()
+    s = _side(device)
+    out = None
+    if defer:
+        s.pending.append(job)
+    else:
+        s.stream.wait_event(event if event is not None else _fork_event(device))
+        with torch.cuda.stream(s.stream):
+            for fn in s.pending:
+                fn()
+            s.pending.clear()
+            out = job()
+    s.parked.extend(operands)
+    return out
 
 
 def _side_join(device) -> None:
-    if _side_pending.get(device.index):
+    s = _sides.get(device.index)
+    if s is None:
+        return
+    if s.pending:
         # deferred side work that no later fork picked up (the block was the last one of this backward): issue it now
-        main = torch.cuda.current_stream(device)
-        side = _side_stream(device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            _run_side_pending(device)
-    parked = _side_parked.get(device.index)
-    if parked:
-        torch.cuda.current_stream(device).wait_stream(_side_stream(device))
-        parked.clear()
-
-
-# Side work whose only dependency is "everything the main stream has issued so far", deferred to the NEXT fork the backward
-# makes anyway.  The persistent dense-block backward is ONE kernel followed by 32 weight-gradient launches: forking the side
-# stream right behind that kernel (one cross-stream edge out of a 0.9 ms node) made the replayed step graph lose its two-lane
-# execution -- the spot branch's backward, which precedes those launches on the side stream, then ran 4.5 ms late
-# (profiles/r05_persistent_bwd_lanes.txt).  Riding on the next block's first per-layer fork keeps the graph's edge structure
-# what it was.
-_side_pending: dict = {}
-
-
-def _defer_to_side(device, fn) -> None:
-    _side_pending.setdefault(device.index, []).append(fn)
-
-
-def _run_side_pending(device) -> None:
-    """Called with the side stream current, after it has waited for an event the main stream recorded later than every
-    deferred job's inputs."""
-    jobs = _side_pending.get(device.index)
-    if jobs:
-        for fn in jobs:
-            fn()
-        jobs.clear()
+        _side_fork(device, lambda: None)
+    if s.parked:
+        torch.cuda.current_stream(device).wait_stream(s.stream)
+        s.parked.clear()
 
 
 # Test instrumentation (tests/test_layerwise_gpu.py): a list that receives, per dense block, the tensors every fused layer
@@ -846,7 +851,7 @@ def _block_bwd_persistent_ok(buf: Tensor, gbuf: Tensor, params, L: int) -> bool:
         return False
     for l in range(L):
         g1, b1, w1, g2, b2, w2 = params[6 * l: 6 * l + 6]
-        if not all(_direct_grad_ok(p) for p in (g1, b1, g2, b2, w2)):
+        if not _direct_all(g1, b1, g2, b2, w2):
             return False
     return True
 
@@ -938,6 +943,51 @@ def dense_block_fwd_persistent(buf: Tensor, params, wcast, stats: "_BlockStats",
     check(Lb.mcl_dense_block_fwd(px, B, H, W, Ct, C0, L, arr, eps1, eps2, stats.mean.data_ptr(), stats.var.data_ptr(),
                                  stats.rstd.data_ptr(), base, err.data_ptr(), SEAM_MAX_SPINS, _stamps_ptr(), _stream()), "mcl_dense_block_fwd")
     return zs
+
+
+class _LayerPlan(NamedTuple):
+    """How ``DenseBlockFn.backward`` runs one layer (``_plan_layer``)."""
+    conv2: str          # "own": 3x3 backward-data + direct weight-gradient kernels | "generic": im2col + own GEMM (conv_generic.py)
+    conv1: str          # conv1 / norm1 backward: "gram" | "single" | "two_pass" (own kernels) | "generic"
+    fix: str            # the single-pass mean terms pending from the layer above: "none" | "fold" | "launch_32" | "launch_all"
+    lanes: bool         # the layer's weight gradients leave the main chain (side stream)
+    opens_pair: bool    # a Gram layer that finds no layer A waiting becomes layer A of a pair
+
+
+def _plan_layer(l: int, cin: int, growth: int, B: int, H: int, W: int, fused1: bool, fused2: bool, w1_direct: bool,
+                w2_direct: bool, kacc_live: bool, side_stream: bool, single_pass: bool, single_max_map: int,
+                gram_min_pixels: int) -> _LayerPlan:
+    """The backward of layer ``l`` (``cin`` input channels) of a dense block on (B, H, W) maps, from facts the caller has
+    worked out: ``fused1`` / ``fused2`` -- the forward kept nothing of norm1's / norm2's output (own conv1 / conv2 kernels);
+    ``w1_direct`` / ``w2_direct`` -- ``_bn1_wrw_ok`` / ``_wrw3_direct_ok``; ``kacc_live`` -- a single-pass layer above left
+    its mean terms pending; then USE_SIDE_STREAM, USE_BN1_SINGLE_PASS, BN1_SINGLE_PASS_MAX_MAP, FUSED_BN1_WRW_MIN_PIXELS.
+
+    conv1: the Gram path (weight gradient fused with the BatchNorm reduction, then the dx pass) from ``gram_min_pixels`` up;
+    below it the single pass on maps of at most ``single_max_map`` pixels, else reduce + dx (two passes).  The dx passes of two
+    consecutive Gram layers run as ONE pass over the channels both read (x and the gradient buffer read once, the buffer
+    written once): layer A = l first applies its term on the 32 channels layer l - 1 produced, in a windowed launch.
+    fix: a single-pass layer needs the pending terms on its own 32 output channels only (its pass applies the rest) -- folded
+    into the dy staging of the flat-tile 3x3 backward-data kernel (it was a 5 us launch in front of every such
+    kernel of the 14 x 14 / 7 x 7 blocks) or as that launch; any other kind of layer applies them to all channels first."""
+    conv2 = "own" if fused2 and w2_direct else "generic"
+    if not fused1:
+        conv1 = "generic"
+    elif w1_direct and B * H * W >= gram_min_pixels:
+        conv1 = "gram"
+    elif single_pass and H * W <= single_max_map:
+        conv1 = "single"
+    else:
+        conv1 = "two_pass"
+    if not kacc_live:
+        fix = "none"
+    elif conv1 != "single":
+        fix = "launch_all"
+    elif growth == 32 and conv2 == "own" and _c3_flat_kernel(W):
+        fix = "fold"
+    else:
+        fix = "launch_32"
+    return _LayerPlan(conv2, conv1, fix, lanes=side_stream and conv1 != "generic" and conv2 == "own",
+                      opens_pair=conv1 == "gram" and l >= 1 and growth == 32 and cin - growth >= 8)
 
 
 class DenseBlockFn(torch.autograd.Function):
@@ -1036,6 +1086,8 @@ class DenseBlockFn(torch.autograd.Function):
         stats, growth, bn2_stats, L, C0 = ctx.meta
         t = ctx.saved_tensors
         buf = t[0]
+        dev = buf.device
+        B, _, H, W = buf.shape
         params = ctx.params
         saved = t[1: 1 + 3 * L]
         wcast = t[1 + 3 * L:]
@@ -1046,6 +1098,7 @@ class DenseBlockFn(torch.autograd.Function):
         if ctx.cap is not None:
             ctx.cap["gin"] = gbuf.clone(memory_format=CL)
             ctx.cap["dz"] = [None] * L
+            ctx.cap["dyc"] = [None] * L
             ctx.cap["gbuf"] = gbuf
         grads = [None] * (6 * L)
         stamp(f"bwd block {buf.shape[2]}x{buf.shape[3]} start (main)")
@@ -1057,7 +1110,6 @@ class DenseBlockFn(torch.autograd.Function):
             if ctx.cap is not None:
                 ctx.cap["dz"] = list(dzs)
                 ctx.cap["dyc"] = list(dycs)
-            dev = buf.device
             gw1s = {}
 
             def _weight_grads():
@@ -1072,13 +1124,11 @@ class DenseBlockFn(torch.autograd.Function):
                     stamp(f"bwd block {buf.shape[2]}x{buf.shape[3]} weight gradients done (side)")
 
             joins = buf.shape[0] * buf.shape[2] * buf.shape[3] >= JOIN_MIN_PIXELS or ctx.first_block
-            direct_w1 = all(_direct_grad_ok(params[6 * l + 2]) and params[6 * l + 2].grad.is_contiguous() for l in range(L))
-            if USE_SIDE_STREAM and direct_w1:
-                # (every gradient goes straight into .grad: nothing to hand back to autograd, the launches can be deferred)
-                _defer_to_side(dev, _weight_grads)
-                _side_park(dev, gbuf, buf, *dzs, *dycs, *zs)
-            else:
-                _weight_grads()
+            # (when every gradient goes straight into .grad nothing is handed back to autograd: the launches can be deferred)
+            lanes = USE_SIDE_STREAM and all(_direct_all(params[6 * l + 2]) and params[6 * l + 2].grad.is_contiguous()
+                                            for l in range(L))
+            _side_fork(dev, _weight_grads, (gbuf, buf, *dzs, *dycs, *zs), lanes=lanes, defer=True)
+            if not lanes:
                 for l in range(L):
                     grads[6 * l + 2] = gw1s[l]
             if STAMPS:
@@ -1100,16 +1150,15 @@ class DenseBlockFn(torch.autograd.Function):
                              gbuf[:, :pair_cin], window=(0, pair_cin - growth))
                 pair_a = None
 
-        def gram_dx(l, dz, w1c, g1, b1, cin, coef):
-            """The dx pass(es) of a Gram-path layer: alone, as layer A of a pair (windowed) or as layer B (paired).  Both
-            backward schedules (side-stream lanes / serial) go through here, so they launch identical kernels."""
+        def gram_dx(opens_pair, dz, w1c, g1, b1, cin, coef):
+            """The dx pass(es) of a Gram-path layer: alone, as layer A of a pair (windowed) or as layer B (paired)."""
             nonlocal pair_a, pair_cin
             mine = (dz, w1c, g1, b1, coef)
             if pair_a is not None:
                 # layer B of a pair: both layers' terms on the channels this layer reads, in one pass
                 dense_bn1_dx_pair(pair_a, mine, buf[:, :cin], stats.mean[:cin], stats.rstd[:cin], gbuf[:, :cin])
                 pair_a = None
-            elif USE_BN1_PAIR and l >= 1 and growth == 32 and cin - growth >= 8:
+            elif opens_pair:
                 # layer A of a pair: only the 32 channels the layer below produced (its 3x3 backward reads them next);
                 # the rest waits for that layer's pass
                 dense_bn1_dx(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin], coef, gbuf[:, :cin],
@@ -1122,154 +1171,80 @@ class DenseBlockFn(torch.autograd.Function):
             a, z, a2 = saved[3 * l: 3 * l + 3]
             w1c, w2c = wcast[2 * l: 2 * l + 2]
             cin = C0 + l * growth
+            c1 = cin + growth
             m2, v2, r2 = bn2_stats[l]
-            d2 = DIRECT_PARAM_GRADS and _direct_grad_ok(g2) and _direct_grad_ok(b2)
-            dy_view = gbuf[:, cin:cin + growth]
-            dw2_done = False
-            fused2 = a2.numel() == 0 and _fused_3x3_ok(z, w2c)
+            x, gx, mean1, rstd1 = buf[:, :cin], gbuf[:, :cin], stats.mean[:cin], stats.rstd[:cin]
+            dy_view = gbuf[:, cin:c1]
+            d2 = _direct_all(g2, b2)
+            d1 = _direct_all(g1, b1)
             fused1 = a.numel() == 0
-            main = torch.cuda.current_stream()
-            side = _side_stream(z.device) if (USE_SIDE_STREAM and fused1 and fused2) else None
-            if side is not None and _wrw3_direct_ok(w2, z, dy_view):
-                # Main chain first, ONE fork per layer, ONE join per block.  Every cross-stream edge of the captured graph
-                # costs the waiting side ~16 us (tools/trace_gaps.py): the per-layer fork + join of the first version
-                # left the GPU idle for 2.4 ms/step.  Here the critical chain (conv3x3_bwd -> bn2_dz -> bn1_bwd) never
-                # waits: the two atomics-bound weight-gradient kernels of the layer start on the side stream once dz
-                # exists (event) and are joined only at the end of the block; dz stays referenced until then.
-                d1 = DIRECT_PARAM_GRADS and _direct_grad_ok(g1) and _direct_grad_ok(b1)
-                fused_wrw = _bn1_wrw_ok(w1) and z.shape[0] * z.shape[2] * z.shape[3] >= FUSED_BN1_WRW_MIN_PIXELS
-                single = not fused_wrw and USE_BN1_SINGLE_PASS and z.shape[2] * z.shape[3] <= BN1_SINGLE_PASS_MAX_MAP
-                fold = None
-                if kacc is not None:
-                    if single:      # this layer's 32 output channels: the mean terms of layer l+1, which no later pass covers
-                        if FOLD_BN1_FIX and growth == 32 and _c3_flat_kernel(z.shape[3]):
-                            c1_ = cin + growth          # applied inside the 3x3 backward-data kernel's dy staging
-                            fold = (buf[:, cin:c1_], stats.mean[cin:c1_], stats.rstd[cin:c1_], kacc[cin:c1_])
-                        else:
-                            dense_bn1_fix(buf, gbuf, cin, growth, stats.mean, stats.rstd, kacc)
-                    else:           # (a two-pass layer after single-pass ones: it will not apply them -- all channels now)
-                        dense_bn1_fix(buf, gbuf, 0, cin + growth, stats.mean, stats.rstd, kacc)
-                        kacc = None
-                dz, dg2, db2, dyc = dense_conv3x3_bwd(dy_view, w2c, z, g2, b2, m2, r2, into_param_grads=d2, fix=fold)
-                dy_w = dyc if dyc is not None else dy_view      # what the 3x3 weight gradient reads
-                if ctx.cap is not None:
-                    ctx.cap["dz"][l] = dz
-                    ctx.cap.setdefault("dyc", [None] * L)[l] = dyc
-                ev = torch.cuda.Event()
-                ev.record(main)
-                if fused_wrw:
-                    # the bottleneck weight gradient rides on the BatchNorm-backward reduction (one pass over dz, x;
-                    # no atomics): it is part of the main chain now, only the 3x3 weight gradient forks off
-                    dg1, db1, coef = dense_bn1_wrw(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin], w1,
-                                                   into_param_grads=d1)
-                    gram_dx(l, dz, w1c, g1, b1, cin, coef)
-                    gw1 = None
-                elif single:
-                    flush_pair()
-                    have_prev = kacc is not None
-                    if not have_prev:
-                        kacc = torch.empty((buf.shape[1], 2), device=buf.device, dtype=torch.float32)
-                    dg1, db1 = dense_bn1_dx_sums(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin],
-                                                 gbuf[:, :cin], kacc, have_prev, into_param_grads=d1)
-                else:
-                    flush_pair()
-                    dg1, db1 = dense_bn1_bwd(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin],
-                                             gbuf[:, :cin], into_param_grads=d1)
-                side.wait_event(ev)
-                with torch.cuda.stream(side):
-                    _run_side_pending(z.device)         # (deferred weight gradients of the block before: persistent backward)
-                    dense_conv3x3_wrw(dy_w, z, g2, b2, m2, r2, w2)
-                    if not fused_wrw:
-                        gw1 = conv1x1_wrw(dz, buf[:, :cin], w1, bn=(g1, b1, stats.mean[:cin], stats.rstd[:cin]))
-                _side_park(z.device, dz, gbuf, z, buf, dy_w)
-                grads[6 * l: 6 * l + 6] = [dg1, db1, gw1, dg2, db2, None]
-                continue
-            gram_here = fused1 and _bn1_wrw_ok(w1) and z.shape[0] * z.shape[2] * z.shape[3] >= FUSED_BN1_WRW_MIN_PIXELS
-            if not gram_here:
-                flush_pair()        # (a pending layer A: its term on the lower channels, before any other kind of pass)
-            main = torch.cuda.current_stream()
-            side = _side_stream(z.device) if (USE_SIDE_STREAM and fused1 and fused2) else None
-            sp_here = (USE_BN1_SINGLE_PASS and fused1 and z.shape[2] * z.shape[3] <= BN1_SINGLE_PASS_MAX_MAP
-                       and not gram_here)
+            fused2 = a2.numel() == 0 and _fused_3x3_ok(z, w2c)
+            plan = _plan_layer(l, cin, growth, B, H, W, fused1, fused2, fused1 and _bn1_wrw_ok(w1),
+                               fused2 and _wrw3_direct_ok(w2, z, dy_view), kacc is not None, USE_SIDE_STREAM,
+                               USE_BN1_SINGLE_PASS, BN1_SINGLE_PASS_MAX_MAP, FUSED_BN1_WRW_MIN_PIXELS)
+            # ---- the mean terms the single-pass layer above left pending
             fold = None
-            if kacc is not None:
-                if sp_here:                                     # the previous pass's mean terms: this layer's 32 output channels
-                    if (FOLD_BN1_FIX and growth == 32 and fused2 and _c3_flat_kernel(z.shape[3])
-                            and _wrw3_direct_ok(w2, z, dy_view)):
-                        c1_ = cin + growth
-                        fold = (buf[:, cin:c1_], stats.mean[cin:c1_], stats.rstd[cin:c1_], kacc[cin:c1_])
-                    else:
-                        dense_bn1_fix(buf, gbuf, cin, growth, stats.mean, stats.rstd, kacc)
-                else:                                           # a two-pass layer follows: it will not apply them -- all channels now
-                    dense_bn1_fix(buf, gbuf, 0, cin + growth, stats.mean, stats.rstd, kacc)
-                    kacc = None
-            if fold is not None:
-                # (the same two kernels as the side-stream schedule: backward-data with the folded correction first, then the
-                # weight gradient on the corrected copy)
+            if plan.fix == "fold":              # this layer's 32 output channels, inside the 3x3 backward-data kernel's dy staging
+                fold = (buf[:, cin:c1], stats.mean[cin:c1], stats.rstd[cin:c1], kacc[cin:c1])
+            elif plan.fix == "launch_32":       # the same channels (no later pass covers them), as a launch of its own
+                dense_bn1_fix(buf, gbuf, cin, growth, stats.mean, stats.rstd, kacc)
+            elif plan.fix == "launch_all":      # (this layer's pass will not apply them -- all channels now)
+                dense_bn1_fix(buf, gbuf, 0, c1, stats.mean, stats.rstd, kacc)
+                kacc = None
+            # ---- conv2 <- relu2 <- norm2
+            dw2 = None
+            if plan.conv2 == "own":
+                # fused forward: a2 = relu(bn2(z)) was never stored.  dy is read in place from the gradient buffer (row stride
+                # C_total); with a folded correction the corrected copy comes back for the weight gradient
                 dz, dg2, db2, dyc = dense_conv3x3_bwd(dy_view, w2c, z, g2, b2, m2, r2, into_param_grads=d2, fix=fold)
-                dw2_done = dense_conv3x3_wrw(dyc, z, g2, b2, m2, r2, w2)
-                assert dw2_done
-                dw2 = None
-            elif fused2:
-                # fused forward: a2 = relu(bn2(z)) was never stored.  Both kernels read dy in place from the gradient
-                # buffer (row stride C_total): no contiguous copy, no MIOpen call
-                if side is not None:
-                    side.wait_stream(main)                      # this layer's slice of gbuf is final
-                    with torch.cuda.stream(side):
-                        dw2_done = dense_conv3x3_wrw(dy_view, z, g2, b2, m2, r2, w2)
-                else:
-                    dw2_done = dense_conv3x3_wrw(dy_view, z, g2, b2, m2, r2, w2)
-            if fold is not None:
-                pass
-            elif dw2_done:
-                dz, dg2, db2, _ = dense_conv3x3_bwd(dy_view, w2c, z, g2, b2, m2, r2, into_param_grads=d2)
-                dw2 = None
             else:
-                dy = dy_view                                  # (read in place through its row stride)
+                dyc = None
                 if a2.numel() == 0:
                     a2 = torch.empty_like(z, memory_format=CL)
                     bn_act_fwd(z, g2, b2, m2, r2, True, a2)
-                da2, dw2 = _conv_bwd(dy, a2, w2c, w2, 1, ctx.kept_cols.pop(l, None))
+                da2, dw2 = _conv_bwd(dy_view, a2, w2c, w2, 1, ctx.kept_cols.pop(l, None))
                 dz = torch.empty_like(z, memory_format=CL)
-                dg2, db2 = bn_act_bwd(dense_cl(da2), z, g2, b2, m2, r2, True, dz, False,
-                                      into_param_grads=d2)
-            d1 = DIRECT_PARAM_GRADS and _direct_grad_ok(g1) and _direct_grad_ok(b1)
-            if fused1:
-                # fused forward: nothing of norm1's output was kept.  Weight gradient with BN1+ReLU recomputed from the
-                # concat buffer; data gradient + BN1 backward without materialising da
-                bn1 = (g1, b1, stats.mean[:cin], stats.rstd[:cin])
-                if gram_here:
-                    dw1 = ("direct", None)
-                    dg1, db1, coef = dense_bn1_wrw(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin], w1,
-                                                   into_param_grads=d1)
-                    gram_dx(l, dz, w1c, g1, b1, cin, coef)
-                    if side is not None:
-                        main.wait_stream(side)
-                    grads[6 * l: 6 * l + 6] = [dg1, db1, None, dg2, db2, None if (dw2_done or dw2 is None) else _wgrad(w2, dw2)]
-                    continue
-                if side is not None and dw2_done:
-                    side.wait_stream(main)                      # dz is ready
-                    with torch.cuda.stream(side):
-                        dw1 = ("direct", conv1x1_wrw(dz, buf[:, :cin], w1, bn=bn1))
-                else:
-                    dw1 = ("direct", conv1x1_wrw(dz, buf[:, :cin], w1, bn=bn1))
-                if sp_here:
-                    have_prev = kacc is not None                # (the same kernels as the side-stream schedule above)
-                    if not have_prev:
-                        kacc = torch.empty((buf.shape[1], 2), device=buf.device, dtype=torch.float32)
-                    dg1, db1 = dense_bn1_dx_sums(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin],
-                                                 gbuf[:, :cin], kacc, have_prev, into_param_grads=d1)
-                else:
-                    dg1, db1 = dense_bn1_bwd(dz, w1c, buf[:, :cin], g1, b1, stats.mean[:cin], stats.rstd[:cin],
-                                             gbuf[:, :cin], into_param_grads=d1)
-                if side is not None:
-                    main.wait_stream(side)                      # join: dz / dy may be released or overwritten now
+                dg2, db2 = bn_act_bwd(dense_cl(da2), z, g2, b2, m2, r2, True, dz, False, into_param_grads=d2)
+            dy_w = dyc if dyc is not None else dy_view      # what the 3x3 weight gradient reads
+            if ctx.cap is not None:
+                ctx.cap["dz"][l] = dz
+                ctx.cap["dyc"][l] = dyc
+            # ---- fork: ONE per layer, ONE join per block.  The critical chain (conv3x3_bwd -> bn1 pass(es)) never waits: the
+            # layer's weight gradients start on the side stream once dz exists and are joined only at the end of the block
+            ev = _fork_event(dev) if plan.lanes else None
+            # ---- conv1 <- relu1 <- norm1 on the main chain
+            if plan.conv1 != "gram":
+                flush_pair()        # (a pending layer A: its term on the lower channels, before any other kind of pass)
+            gw1 = None
+            if plan.conv1 == "gram":
+                # the bottleneck weight gradient rides on the BatchNorm-backward reduction (one pass over dz, x; no atomics):
+                # it is part of the main chain, only the 3x3 weight gradient is left for the fork
+                dg1, db1, coef = dense_bn1_wrw(dz, w1c, x, g1, b1, mean1, rstd1, w1, into_param_grads=d1)
+                gram_dx(plan.opens_pair, dz, w1c, g1, b1, cin, coef)
+            elif plan.conv1 == "single":
+                have_prev = kacc is not None
+                if not have_prev:
+                    kacc = torch.empty((buf.shape[1], 2), device=dev, dtype=torch.float32)
+                dg1, db1 = dense_bn1_dx_sums(dz, w1c, x, g1, b1, mean1, rstd1, gx, kacc, have_prev, into_param_grads=d1)
+            elif plan.conv1 == "two_pass":
+                dg1, db1 = dense_bn1_bwd(dz, w1c, x, g1, b1, mean1, rstd1, gx, into_param_grads=d1)
             else:
                 da, dw1 = _conv1x1_bwd(dz, a, w1c, w1)
-                dg1, db1 = bn_act_bwd(da, buf[:, :cin], g1, b1, stats.mean[:cin],
-                                      stats.rstd[:cin], True, gbuf[:, :cin], True, into_param_grads=d1)
-            gw1 = dw1[1] if isinstance(dw1, tuple) else (None if dw1 is None else _wgrad(w1, dw1))
-            grads[6 * l: 6 * l + 6] = [dg1, db1, gw1, dg2, db2, None if (dw2_done or dw2 is None) else _wgrad(w2, dw2)]
+                dg1, db1 = bn_act_bwd(da, x, g1, b1, mean1, rstd1, True, gx, True, into_param_grads=d1)
+                gw1 = None if dw1 is None else _wgrad(w1, dw1)
+
+            # ---- the weight gradients the main chain has not produced on its way (norm1 + relu1 / norm2 + relu2 recomputed
+            # in-kernel from the concat buffer / z): on the side stream behind the fork, or here
+            def weight_grads():
+                if plan.conv2 == "own":
+                    done = dense_conv3x3_wrw(dy_w, z, g2, b2, m2, r2, w2)
+                    assert done
+                if plan.conv1 in ("single", "two_pass"):
+                    return conv1x1_wrw(dz, x, w1, bn=(g1, b1, mean1, rstd1))
+                return gw1
+
+            gw1 = _side_fork(dev, weight_grads, (dz, gbuf, z, buf, dy_w), lanes=plan.lanes, event=ev)
+            grads[6 * l: 6 * l + 6] = [dg1, db1, gw1, dg2, db2, None if dw2 is None else _wgrad(w2, dw2)]
         # The tensors the side stream still reads stay parked (referenced) until a join.  Joining after every block makes
         # the main chain wait whenever the side stream runs behind; the small maps can afford to keep their tensors alive
         # (tens of MB) until a later block joins: 14.58 -> 14.28 ms/step on configs[1].  The network's first block is the
@@ -1373,7 +1348,7 @@ class Conv0Fn(torch.autograd.Function):
         if ctx.cap is not None:
             ctx.cap["dy"] = dy
         B, _, H, W = x.shape
-        if DIRECT_PARAM_GRADS and _direct_grad_ok(w) and dy.dtype == torch.bfloat16:
+        if _direct_all(w) and dy.dtype == torch.bfloat16:
             L = _lib.lib()
             ws = _ws(L.mcl_conv0_wrw_workspace_floats(B, H, W), x.device)
             tgt, in_place = _grad_target_khwc(w)
@@ -1472,7 +1447,7 @@ class StemTailFn(torch.autograd.Function):
         g = torch.empty_like(x, memory_format=CL)           # un-pooled gradient (gather, deterministic)
         check(_lib.lib().mcl_maxpool3s2_nhwc_bf16_bwd_ld(idx.data_ptr(), pdy, lddy, g.data_ptr(), B, H, W, C, _stream()),
               "mcl_maxpool bwd")
-        direct = DIRECT_PARAM_GRADS and _direct_grad_ok(gamma) and _direct_grad_ok(beta)
+        direct = _direct_all(gamma, beta)
         dg, db = bn_act_bwd(g, x, gamma, beta, mean, rstd, True, g, False, into_param_grads=direct)   # dx in place of g
         if ctx.cap is not None:
             ctx.cap["dx"] = g
@@ -1585,12 +1560,9 @@ class TransitionFn(torch.autograd.Function):
         B, C, H, W = buf.shape
         Co = w16.shape[0]
         _rows(dy)                                             # channels-last (possibly channel-sliced) view
-        main = torch.cuda.current_stream()
-        deferred = (USE_SIDE_STREAM and DIRECT_PARAM_GRADS and _direct_grad_ok(w)
-                    and w.grad.is_contiguous())
-        if deferred:
-            ev = torch.cuda.Event()
-            ev.record(main)                                   # dy is final
+        # (the weight gradient leaves the main chain when it goes straight into .grad: nothing comes back from the other stream)
+        lanes = USE_SIDE_STREAM and _direct_all(w) and w.grad.is_contiguous()
+        ev = _fork_event(buf.device) if lanes else None       # dy is final
         # dp = dy . W: (S/4, Co) x (Co, C), the weight consumed in place as the reduction-major operand of mcl_gemm_bf16
         # (csrc/gemm_bf16.hip); dy may be the channel slice [:Co] of the next block's gradient buffer (row stride lddy)
         pdy, Sq, Co_, lddy = _rows(dy)
@@ -1600,7 +1572,7 @@ class TransitionFn(torch.autograd.Function):
                                        1.0, 2, None, None, 0, 0, None, 0, None, 0, 1, None, 0, _stream()),
               "mcl_gemm_bf16 (transition backward-data)")
         dx = torch.empty_like(buf, memory_format=CL)
-        direct = DIRECT_PARAM_GRADS and _direct_grad_ok(gamma) and _direct_grad_ok(beta)
+        direct = _direct_all(gamma, beta)
         if direct:
             dg, db = gamma.grad, beta.grad
         else:
@@ -1612,17 +1584,9 @@ class TransitionFn(torch.autograd.Function):
                                        beta.data_ptr(), stats.mean.data_ptr(), stats.rstd.data_ptr(), ws.data_ptr(),
                                        dg.data_ptr(), db.data_ptr(), int(direct), dx.data_ptr(), C, _stream()),
               "mcl_bn_act_avgpool_bwd")
-        if deferred:
-            # weight gradient (atomics-bound, needs only dy and p) on the side stream; joined by the dense block that
-            # follows in the backward order
-            side = _side_stream(buf.device)
-            side.wait_event(ev)
-            with torch.cuda.stream(side):
-                _run_side_pending(buf.device)            # (deferred weight gradients of the dense block before)
-                dw = conv1x1_wrw(dy, p, w)
-            _side_park(buf.device, dy, p)
-        else:
-            dw = conv1x1_wrw(dy, p, w)                        # dW += dy^T p, straight into w.grad when it exists
+        # dW += dy^T p, straight into w.grad when it exists (it needs only dy and p): on the side stream -- behind the deferred
+        # weight gradients of the dense block before, joined by the dense block that follows in the backward order -- or here
+        dw = _side_fork(buf.device, lambda: conv1x1_wrw(dy, p, w), (dy, p), lanes=lanes, event=ev)
         gw = None if dw is None else dw.view_as(w).to(w.dtype)
         if ctx.cap is not None:
             ctx.cap.update({"dy": dy, "dp": dp, "dx": dx.clone(memory_format=CL)})   # (dx becomes a gradient buffer, in place)
@@ -1661,7 +1625,7 @@ class BNGlobalPoolFn(torch.autograd.Function):
             g = g.float()
         px, S, _, ld = _rows(x)
         dx = torch.empty_like(x, memory_format=CL)
-        direct = DIRECT_PARAM_GRADS and _direct_grad_ok(gamma) and _direct_grad_ok(beta)
+        direct = _direct_all(gamma, beta)
         if direct:
             dg, db = gamma.grad, beta.grad
         else:

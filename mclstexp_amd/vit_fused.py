@@ -147,19 +147,14 @@ def _param_grads(dy: Tensor, x: Tensor, lin, rows: int, grads: dict) -> None:
     """grads[lin.weight], grads[lin.bias] for y = x W^T + b given dy; on the side stream when both are written in place."""
     from . import densenet_fused as dn
     direct = _grad_target(lin.weight)[1] and (lin.bias is None or _grad_target(lin.bias)[1])
-    if SIDE_WGRAD and dn.USE_SIDE_STREAM and direct:
-        main = torch.cuda.current_stream()
-        side = dn._side_stream(dy.device)
-        side.wait_stream(main)                # dy is final on the main stream
-        with torch.cuda.stream(side):
-            grads[lin.weight] = linear_wgrad(dy, x, lin.weight, rows)
-            if lin.bias is not None:
-                grads[lin.bias] = bias_grad(dy, lin.bias, rows)
-        dn._side_park(dy.device, dy, x)
-        return
-    grads[lin.weight] = linear_wgrad(dy, x, lin.weight, rows)
-    if lin.bias is not None:
-        grads[lin.bias] = bias_grad(dy, lin.bias, rows)
+
+    def job():
+        grads[lin.weight] = linear_wgrad(dy, x, lin.weight, rows)
+        if lin.bias is not None:
+            grads[lin.bias] = bias_grad(dy, lin.bias, rows)
+
+    # (forked where dy is final on the main stream)
+    dn._side_fork(dy.device, job, (dy, x), lanes=SIDE_WGRAD and dn.USE_SIDE_STREAM and direct)
 
 
 def linear_wgrad(dy: Tensor, x: Tensor, w: Tensor, rows: int):

@@ -120,3 +120,62 @@ def test_retrieval_filter_plan_keeps_the_expected_list_inside_its_capacity():
             expect = r * n / ns
             assert expect >= 1.4 * k, (n, k)
             assert expect * (1 + 4 / r ** 0.5) < cap, (n, k, expect, cap)      # four standard deviations of the count
+
+
+def test_dense_backward_layer_plan_at_the_benchmark_shapes(monkeypatch):
+    """densenet_fused._plan_layer, the one decision table of DenseBlockFn.backward (booleans and integers only), walked in
+    backward order over the four DenseNet-121 blocks at bench.py's default workload, the way the backward walks them (the only
+    state it carries between layers: single-pass mean terms pending, a layer A waiting for its pair)."""
+    import sys
+
+    import bench
+    from mclstexp_amd import densenet_fused as dn
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    args = bench.parse()
+    assert (args.batch, args.image) == (128, 224)
+    growth = 32
+    blocks = [(6, 64, args.image // 4), (12, 128, args.image // 8), (24, 256, args.image // 16), (16, 512, args.image // 32)]
+
+    def walk(L, C0, hw, B, own=True, side=True):
+        """[(l, plan, role)] of one block; role of a Gram layer: "A" / "B" of a pair or "alone"."""
+        out, kacc, pending = [], False, False
+        for l in range(L - 1, -1, -1):
+            p = dn._plan_layer(l, C0 + l * growth, growth, B, hw, hw, own, own, own, own, kacc, side,
+                               dn.USE_BN1_SINGLE_PASS, dn.BN1_SINGLE_PASS_MAX_MAP, dn.FUSED_BN1_WRW_MIN_PIXELS)
+            role = None
+            if p.conv1 == "gram":
+                role = "B" if pending else ("A" if p.opens_pair else "alone")
+                pending = role == "A"
+            else:
+                pending = False                                 # (the executor flushes a waiting layer A here)
+            kacc = p.conv1 == "single" or (kacc and p.fix != "launch_all")
+            out.append((l, p, role))
+        return out
+
+    for side in (True, False):
+        for L, C0, hw in blocks[:2]:                            # 56 x 56, 28 x 28: Gram path, dx passes in pairs
+            steps = walk(L, C0, hw, args.batch, side=side)
+            assert all(p.conv2 == "own" and p.conv1 == "gram" and p.fix == "none" and p.lanes == side for _, p, _ in steps)
+            assert all(p.opens_pair == (l >= 1) for l, p, _ in steps)       # layer 0 never opens a pair: alone unless it closes one
+            assert [r for _, _, r in steps] == ["A", "B"] * (L // 2)         # (L - 1, L - 2), ..., (1, 0)
+        L, C0, hw = blocks[2]                                   # 14 x 14: single pass, correction folded from the second layer on
+        steps = walk(L, C0, hw, args.batch, side=side)
+        assert all(p.conv2 == "own" and p.conv1 == "single" and p.lanes == side and not p.opens_pair for _, p, _ in steps)
+        assert [p.fix for _, p, _ in steps] == ["none"] + ["fold"] * (L - 1)
+        L, C0, hw = blocks[0]                                   # B = 4: below the Gram threshold, map too large for the single pass
+        steps = walk(L, C0, hw, 4, side=side)
+        assert all(p.conv1 == "two_pass" and p.fix == "none" and p.conv2 == "own" and p.lanes == side for _, p, _ in steps)
+        for L, C0, hw in blocks:                                # fp32 activations: nothing fused, nothing leaves the main chain
+            for B in (4, args.batch):
+                steps = walk(L, C0, hw, B, own=False, side=side)
+                assert all(p == dn._LayerPlan("generic", "generic", "none", False, False) for _, p, _ in steps)
+    # lanes is false whenever USE_SIDE_STREAM is false, whatever else holds
+    import itertools
+    for f1, f2, d1, d2, k, hw, B in itertools.product((False, True), (False, True), (False, True), (False, True), (False, True),
+                                                       (7, 14, 28, 56), (4, 128)):
+        p = dn._plan_layer(3, 160, growth, B, hw, hw, f1, f2, d1, d2, k, False, True, 256, 50000)
+        assert p.lanes is False
+        q = dn._plan_layer(3, 160, growth, B, hw, hw, f1, f2, d1, d2, k, True, True, 256, 50000)
+        assert q.lanes == (f1 and f2 and d2) and q[:3] == p[:3]      # the schedule changes nothing else
+        assert (p.fix == "none") == (not k) and (p.fix == "fold") <= (p.conv1 == "single" and p.conv2 == "own" and hw < 17)
+        assert (p.fix == "launch_all") == (k and p.conv1 != "single")

@@ -66,6 +66,17 @@ def _q(a, b, q=0.999):
 
 @pytest.mark.parametrize("B,HW", [(128, 224)])
 def test_dense_layers_teacher_forced_at_benched_shapes(B, HW):
+    _teacher_forced(B, HW, side_stream=True)
+
+
+@pytest.mark.parametrize("B,HW", [(128, 224)])
+def test_dense_layers_teacher_forced_on_one_stream(B, HW):
+    """The same with the weight gradients issued on the main stream (USE_SIDE_STREAM = False, the schedule the serial profiles
+    trace): both schedules run one per-layer body, so both record what their kernels consumed and produced."""
+    _teacher_forced(B, HW, side_stream=False)
+
+
+def _teacher_forced(B, HW, side_stream):
     from mclstexp_amd import backbones, densenet_fused as dn
     torch.manual_seed(0)
     enc = backbones.ImageEncoder().to(DEV).to(memory_format=torch.channels_last).train()
@@ -73,6 +84,8 @@ def test_dense_layers_teacher_forced_at_benched_shapes(B, HW):
     x = torch.rand((B, 3, HW, HW), device=DEV, generator=g).contiguous(memory_format=torch.channels_last)
     dy_feat = (torch.rand((B, 1024), device=DEV, generator=g) - 0.5)
     dn.reset_fallbacks()
+    keep = dn.USE_SIDE_STREAM
+    dn.USE_SIDE_STREAM = side_stream
     dn.CAPTURE_BLOCKS, dn.CAPTURE_MISC = [], []
     try:
         y = enc.forward_fused(x, torch.bfloat16)
@@ -81,6 +94,7 @@ def test_dense_layers_teacher_forced_at_benched_shapes(B, HW):
         blocks, misc = dn.CAPTURE_BLOCKS, dn.CAPTURE_MISC
     finally:
         dn.CAPTURE_BLOCKS = dn.CAPTURE_MISC = None
+        dn.USE_SIDE_STREAM = keep
     assert dn.fallback_counts() == {}, dn.fallback_counts()
     assert len(blocks) == 4
     feats = enc.model[0]
