@@ -812,6 +812,37 @@ int mcl_expr_metrics(const void* pred, int64_t ld_pred, int32_t pred_dtype, cons
                      int32_t true_dtype, const int64_t* offsets, int32_t S, int32_t G, int32_t n_heg, double* r,
                      double* true_mean, int64_t* heg, double* summary, double* work, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- gene significance (csrc/gene_significance.hip; added
+ * under ABI 13: new entry points only).  The second output of get_R (utils.py:52-65: scipy.stats.pearsonr's two-sided
+ * p-value per gene) and the gene table of tutorial.ipynb's third cell.  All fp64, deterministic, no atomics.
+ *
+ * mcl_pearson_pvalue: r (S x G) as mcl_expr_metrics writes it, offsets[S + 1] the same device-resident int64 segment
+ *   boundaries; n = the segment's length, a = n / 2 - 1.  Per element, into p and neglog10p (both S x G):
+ *     r NaN (or n < 2)  -> both NaN;
+ *     n == 2            -> p = 1, neglog10p = 0 (scipy's rule);
+ *     |r| >= 1          -> p = 0, neglog10p = +inf;
+ *     otherwise         log p = log 2 + log I_x(a, a), x = (1 - |r|) / 2: the prefactor lgamma(2a) - 2 lgamma(a) + a log x
+ *                       + a log1p(-x) - log a plus the log of the continued fraction (modified Lentz, at most 1000 trips;
+ *                       an element that has not converged by then is NaN, never a wrong number), clamped at 0;
+ *                       neglog10p = -log p / ln 10 -- evaluated in log space, so it stays finite where p underflows;
+ *                       p = exp(log p), which underflows to 0 as scipy's does.
+ *   Every element depends on (r, n) alone: a segment inside a batch is bit-identical to the same segment alone.
+ * mcl_gene_rank: neglog10p and r (S x G).  Per gene g, slides walked in index order:
+ *     mean[g]        the mean of neglog10p[:, g] over its non-NaN entries (pandas mean(axis=1), skipna): NaN if there is
+ *                    none, +inf if one of them is +inf;
+ *     n_defined[g]   how many entries are not NaN;
+ *     best_slide[g]  the first slide that attains the maximum over the non-NaN entries (pandas idxmax), -1 if none;
+ *     best_value[g], best_r[g]   neglog10p and r at that slide (NaN if none);
+ *   then order[G] int64: order[k] = the gene of rank k by descending mean -- exact rank by counting, equal means by
+ *   ascending gene index, NaN means last.  The order is always full; top_n (1 <= top_n <= G) is how many leading
+ *   entries the caller means to read and changes no result.
+ * Both: S <= 65535 and G <= 1048576, MCL_EUNSUPPORTED beyond.                                                       */
+int mcl_pearson_pvalue(const double* r, const int64_t* offsets, int32_t S, int32_t G, double* p, double* neglog10p,
+                       mcl_stream_t stream);
+int mcl_gene_rank(const double* neglog10p, const double* r, int32_t S, int32_t G, int32_t top_n, double* mean,
+                  int32_t* n_defined, int64_t* order, int32_t* best_slide, double* best_value, double* best_r,
+                  mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- spatial-domain clustering (ABI 12; csrc/cluster.hip)
  * The reference's cluster() (utils.py:67-79): PCA -> k-means -> ARI / NMI against given labels, for S slides per call.
  * Common contract: row-stacked row-major device matrices, offsets[S + 1] device-resident int64 with offsets[0] = 0, every

@@ -212,6 +212,8 @@ PROTOTYPES = {
     "mcl_topk_rows_indexed": [c_p, c_l, c_p, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     "mcl_knn_weighted_average": [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
     "mcl_expr_metrics": [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_pearson_pvalue": [c_p, c_p, c_i, c_i, c_p, c_p, c_p],
+    "mcl_gene_rank": [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_pca_gram": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     "mcl_pca_project": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_kmeans": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, C.c_uint64, c_i, c_d, c_i, c_p, c_p, c_p, c_p, c_p, c_p,

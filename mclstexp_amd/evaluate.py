@@ -13,6 +13,7 @@ batch is bit-identical to the same fold scored alone).  Arrays move to the devic
 the HIP library these functions raise ``RuntimeError``.
 
     python -m mclstexp_amd.evaluate --dataset her2st --embedding_dir DIR --expressions F1.npy F2.npy ... [--json OUT]
+                                    [--save_pred DIR]
 """
 from __future__ import annotations
 
@@ -36,6 +37,7 @@ ArrayLike = Union[np.ndarray, Tensor]
 PRESETS = {"her2st": (200, 1), "cscc": (600, 2), "10x": (200, 2)}
 N_HEG = 50
 SUMMARY_KEYS = ("heg_pcc", "hvg_pcc", "mse", "mae")
+PRED_FILE = "matched_spot_expression_pred_mclSTExp.npy"
 _DTYPE_CODE = {torch.float32: 0, torch.float64: 1}
 
 
@@ -173,12 +175,13 @@ def _cat_rows(parts: Sequence[ArrayLike]) -> ArrayLike:
 def leave_one_slide_out(image_embeddings: Optional[Sequence[ArrayLike]], spot_embeddings: Optional[Sequence[ArrayLike]],
                         expressions: Sequence[ArrayLike], top_k: int, ord: int,
                         per_fold: Optional[Callable[[int], Tuple[Sequence[ArrayLike], Sequence[ArrayLike]]]] = None,
-                        n_heg: int = N_HEG) -> Dict[str, object]:
+                        n_heg: int = N_HEG, return_preds: bool = False) -> Dict[str, object]:
     """The reference's protocol (evel_her2st.py:140-226): fold f queries slide f's image embeddings against the spot
     embeddings and expressions of all OTHER slides; every list holds one (spots, ·) array per slide.  ``per_fold(f)``
     -> (image_embeddings, spot_embeddings) supplies fold-specific embeddings (the reference loads ``embeddings_{f}/``
     from fold f's own checkpoint); without it one model's embeddings serve all folds.  Retrieval runs per fold, the
-    scoring of all folds is one call.  Returns what ``score_folds`` returns."""
+    scoring of all folds is one call.  Returns what ``score_folds`` returns; with ``return_preds`` also ``preds``: every
+    slide's (spots, genes) prediction as a numpy array (what ``mclstexp_amd.genes`` ranks genes from)."""
     n = len(expressions)
     if n < 2:
         raise ValueError("leave-one-slide-out needs >= 2 slides")
@@ -191,7 +194,10 @@ def leave_one_slide_out(image_embeddings: Optional[Sequence[ArrayLike]], spot_em
         key = _cat_rows([spot[i] for i in rest])
         expr = _cat_rows([expressions[i] for i in rest])
         preds.append(_predict_device(key, expr, img[f], top_k, ord))
-    return score_folds(preds, list(expressions), n_heg)
+    res = score_folds(preds, list(expressions), n_heg)
+    if return_preds:
+        res["preds"] = [p.cpu().numpy() for p in preds]
+    return res
 
 
 # --------------------------------------------------------------------------- CLI
@@ -204,6 +210,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--expressions", required=True, nargs="+",
                    help="one preprocessed_matrix.npy per slide, (G, N), in slide order")
     p.add_argument("--json", default=None, help="also write per-fold and average scores to this file")
+    p.add_argument("--save_pred", default=None, metavar="DIR",
+                   help=f"also write every slide's prediction to DIR/<slide index>/{PRED_FILE}, (G, N)")
     return p.parse_args(argv)
 
 
@@ -242,6 +250,22 @@ def check_layout(images: Sequence[Optional[np.ndarray]], spots: Sequence[np.ndar
                          f"{expressions[fold].shape[0]} expression rows")
 
 
+def save_predictions(root: str, preds: Sequence[np.ndarray]) -> List[str]:
+    """Writes slide i's (spots, genes) prediction to ``root/<i>/matched_spot_expression_pred_mclSTExp.npy`` stored (G, N)
+    -- the file the reference's tutorial.ipynb reads per slide (``python -m mclstexp_amd.genes --pred``).  Returns the
+    paths in slide order."""
+    paths = []
+    for i, p in enumerate(preds):
+        a = np.asarray(p)
+        if a.ndim != 2:
+            raise ValueError(f"prediction of slide {i}: expected a (spots, genes) array, got {a.shape}")
+        d = os.path.join(root, str(i))
+        os.makedirs(d, exist_ok=True)
+        paths.append(os.path.join(d, PRED_FILE))
+        np.save(paths[-1], np.ascontiguousarray(a.T))
+    return paths
+
+
 def format_report(res: Dict[str, object]) -> str:
     """The four lines the reference's scripts print last (evel_her2st.py:223-226)."""
     return "\n".join([f"avg heg pcc: {res['heg_pcc']:.4f}", f"avg hvg pcc: {res['hvg_pcc']:.4f}",
@@ -267,8 +291,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         check_layout(images, spots, expressions, f)
         return images, spots
 
-    res = leave_one_slide_out(None, None, expressions, top_k, ord_, per_fold=per_fold)
+    res = leave_one_slide_out(None, None, expressions, top_k, ord_, per_fold=per_fold,
+                              return_preds=args.save_pred is not None)
     print(format_report(res))
+    if args.save_pred:
+        save_predictions(args.save_pred, res["preds"])
     if args.json:
         doc = {k: _json_value(res[k]) for k in SUMMARY_KEYS}
         doc.update(dataset=args.dataset, top_k=top_k, ord=ord_,
