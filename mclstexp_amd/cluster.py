@@ -18,68 +18,26 @@ the HIP library these functions raise ``RuntimeError``.
 from __future__ import annotations
 
 import argparse
-import json
 import sys
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _arrays, _lib, ops
+from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, stack_rows, upload, write_json
 from ._lib import check
-
-Tensor = torch.Tensor
-ArrayLike = Union[np.ndarray, Tensor]
 
 N_COMPS = 9          # sc.pp.pca(tmp, n_comps=9), utils.py:71
 MAX_DIM = 64         # D <= 64 and K <= 64 (csrc/cluster.hip)
 MAX_ROWS = 50000     # per segment: the pair counts of the ARI stay inside int64
 MAX_LABEL = 1024     # label values in [0, 1024)
 MAX_TABLE = 12288    # distinct(a) * distinct(b) per segment
-_DTYPE_CODE = {torch.float32: 0, torch.float64: 1}
-
-
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("mclstexp_amd.cluster: no GPU available (HIP kernels, no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 def validate_offsets(offsets: Optional[Sequence[int]], rows: int, min_rows: int = 1) -> np.ndarray:
     """offsets[0] = 0, offsets[-1] = rows, every segment holds min_rows .. 50 000 rows.  None: one segment.  int64."""
-    if offsets is None:
-        offsets = [0, rows]
-    off = np.asarray(offsets)
-    if off.ndim != 1 or off.size < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError(f"offsets must be a 1-D integer array of S + 1 >= 2 entries, got {off!r}")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != rows:
-        raise ValueError(f"offsets must run from 0 to the number of rows ({rows}), got {off[0]} .. {off[-1]}")
-    seg = np.diff(off)
-    if (seg < min_rows).any() or (seg > MAX_ROWS).any():
-        raise ValueError(f"every segment needs {min_rows} .. {MAX_ROWS} rows; segment sizes {seg.tolist()}")
-    if off.size - 1 > 65535:
-        raise ValueError("at most 65535 segments per call")
-    return off
-
-
-def _matrix(x: ArrayLike, name: str, dev: torch.device) -> Tensor:
-    """A row-major float32 / float64 device matrix (no copy when it already is one; other dtypes become float64 on the
-    host)."""
-    t = x if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x))
-    if t.dim() != 2:
-        raise ValueError(f"{name}: expected a 2-D array, got shape {tuple(t.shape)}")
-    if t.dtype not in _DTYPE_CODE:
-        if t.is_cuda:
-            raise ValueError(f"{name}: device tensors must be float32 or float64, got {t.dtype}")
-        t = t.to(torch.float64)
-    if t.is_cuda and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1]:
-        return t
-    if t.is_cuda:
-        out = torch.empty(tuple(t.shape), device=dev, dtype=t.dtype)
-        out.copy_(t)
-        return out
-    return t.contiguous().to(dev)
+    return _arrays.validate_offsets(offsets, rows, min_rows, MAX_ROWS, max_segments=65535, none_is_one=True)
 
 
 def _labels_i32(v: ArrayLike, name: str, dev: torch.device) -> Tensor:
@@ -114,19 +72,18 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     if n_comps >= int(m.min()):
         raise ValueError(f"n_comps = {n_comps} needs more than {n_comps} spots and genes in every segment "
                          f"(smallest min(spots, genes) = {int(m.min())})")
-    dev = _device()
+    dev = device("cluster")
     lib = _lib.lib()
-    xd = _matrix(x, "x", dev)
+    xd = matrix(x, "x", dev, FLOAT_CODE, torch.float64)
     S = off.size - 1
-    goff = np.concatenate([[0], np.cumsum(m * m)]).astype(np.int64)
-    eoff = np.concatenate([[0], np.cumsum(m * n_comps)]).astype(np.int64)
-    off_d = torch.from_numpy(off).to(dev)
-    goff_d = torch.from_numpy(goff).to(dev)
-    mean = torch.empty((S, G), device=dev, dtype=torch.float64)
-    gram = torch.empty((int(goff[-1]),), device=dev, dtype=torch.float64)
+    goff, eoff = cumulative_offsets(m * m), cumulative_offsets(m * n_comps)
+    off_d, goff_d = upload(off, dev), upload(goff, dev)
+    e = empty(dev)
+    mean = e((S, G), torch.float64)
+    gram = e((int(goff[-1]),), torch.float64)
     max_rows = int(seg.max())
     st = ops._stream()
-    check(lib.mcl_pca_gram(xd.data_ptr(), xd.stride(0), _DTYPE_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
+    check(lib.mcl_pca_gram(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
                            goff_d.data_ptr(), mean.data_ptr(), gram.data_ptr(), st), "mcl_pca_gram")
     gram_h = gram.cpu().numpy()                      # the one synchronisation of the pipeline
     evec = np.empty((int(eoff[-1]),), dtype=np.float64)
@@ -136,13 +93,10 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
         w, v = np.linalg.eigh(gram_h[goff[s]:goff[s + 1]].reshape(ms, ms))      # ascending
         evals[s] = w[::-1][:n_comps]
         evec[eoff[s]:eoff[s + 1]] = np.ascontiguousarray(v[:, ::-1][:, :n_comps]).reshape(-1)
-    evec_d = torch.from_numpy(evec).to(dev)
-    eval_d = torch.from_numpy(evals).to(dev)
-    eoff_d = torch.from_numpy(eoff).to(dev)
-    loadings = torch.empty((S * G * n_comps,), device=dev, dtype=torch.float64)
-    sign = torch.empty((S, n_comps), device=dev, dtype=torch.float64)
-    z = torch.empty((rows, n_comps), device=dev, dtype=torch.float64)
-    check(lib.mcl_pca_project(xd.data_ptr(), xd.stride(0), _DTYPE_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
+    evec_d, eval_d, eoff_d = upload(evec, dev), upload(evals, dev), upload(eoff, dev)
+    loadings = e((S * G * n_comps,), torch.float64)
+    sign, z = e((S, n_comps), torch.float64), e((rows, n_comps), torch.float64)
+    check(lib.mcl_pca_project(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
                               n_comps, mean.data_ptr(), evec_d.data_ptr(), eoff_d.data_ptr(), eval_d.data_ptr(),
                               loadings.data_ptr(), sign.data_ptr(), z.data_ptr(), st), "mcl_pca_project")
     return {"scores": z, "sign": sign, "explained_variance": np.maximum(evals, 0.0) / (seg[:, None] - 1.0),
@@ -154,33 +108,9 @@ def pca_scores(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     return pca_device(x, offsets, n_comps)["scores"]
 
 
-def _stack_rows(parts: Sequence[ArrayLike], name: str, dev: torch.device) -> Tuple[Tensor, np.ndarray]:
-    """Slides row-stacked into one device matrix (plain copies only) and their offsets."""
-    if not parts:
-        raise ValueError(f"{name}: need at least one slide")
-    ts = [p if isinstance(p, Tensor) else torch.as_tensor(np.asarray(p)) for p in parts]
-    for i, t in enumerate(ts):
-        if t.dim() != 2 or t.shape[1] != ts[0].shape[1]:
-            raise ValueError(f"{name}[{i}]: expected (spots, {ts[0].shape[1]}), got {tuple(t.shape)}")
-    offsets = np.concatenate([[0], np.cumsum([int(t.shape[0]) for t in ts])]).astype(np.int64)
-    if len(ts) == 1:
-        return _matrix(ts[0], name, dev), offsets
-    dtypes = {t.dtype for t in ts}
-    dtype = dtypes.pop() if len(dtypes) == 1 and ts[0].dtype in _DTYPE_CODE else torch.float64
-    out = torch.empty((int(offsets[-1]), ts[0].shape[1]), device=dev, dtype=dtype)
-    for i, t in enumerate(ts):
-        if t.dtype != dtype:
-            if t.is_cuda:
-                raise ValueError(f"{name}[{i}]: device slides must share one dtype (float32 or float64)")
-            t = t.to(dtype)
-        out[offsets[i]:offsets[i + 1]].copy_(t)
-    return out, offsets
-
-
 def pca_scores_slides(xs: Sequence[ArrayLike], n_comps: int = N_COMPS) -> List[Tensor]:
     """One (spots_i, n_comps) device score matrix per slide, all slides in one gram and one project call."""
-    dev = _device()
-    x, off = _stack_rows(xs, "xs", dev)
+    x, off = stack_rows(xs, "xs", device("cluster"))
     z = pca_scores(x, off, n_comps)
     return [z[off[i]:off[i + 1]] for i in range(len(xs))]
 
@@ -253,15 +183,14 @@ def kmeans(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequenc
         R = int(n_init)
     if R < 1 or R > 65535:
         raise ValueError(f"the number of restarts must lie in 1 .. 65535, got {R}")
-    dev = _device()
+    dev = device("cluster")
     lib = _lib.lib()
-    zd = _matrix(z, "z", dev)
+    zd = matrix(z, "z", dev, FLOAT_CODE, torch.float64)
     if zd.dtype != torch.float64:
         raise ValueError("z must be float64 (the PCA scores are)")
-    off_d = torch.from_numpy(off).to(dev)
-    ks_d = torch.from_numpy(ks).to(dev)
-    seeds_d = torch.from_numpy(seeds_h).to(dev) if seeds_h is not None else None
-    e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)  # noqa: E731
+    off_d, ks_d = upload(off, dev), upload(ks, dev)
+    seeds_d = upload(seeds_h, dev) if seeds_h is not None else None
+    e = empty(dev)
     res = {"seed_rows": e((S, R, k_max), torch.int64), "labels_all": e((R, rows), torch.int32),
            "centers_all": e((S, R, k_max, D), torch.float64), "inertia_all": e((S, R), torch.float64),
            "n_iter_all": e((S, R), torch.int32), "labels": e((rows,), torch.int32),
@@ -288,12 +217,12 @@ def cluster_scores(labels_a: ArrayLike, labels_b: ArrayLike,
     if na != nb:
         raise ValueError(f"label vectors differ in length: {na} and {nb}")
     off = validate_offsets(offsets, na)
-    dev = _device()
+    dev = device("cluster")
     lib = _lib.lib()
     a = _labels_i32(labels_a, "labels_a", dev)
     b = _labels_i32(labels_b, "labels_b", dev)
     S = off.size - 1
-    off_d = torch.from_numpy(off).to(dev)
+    off_d = upload(off, dev)
     out = torch.empty((S, 2), device=dev, dtype=torch.float64)
     check(lib.mcl_cluster_scores(a.data_ptr(), b.data_ptr(), off_d.data_ptr(), S, int(np.diff(off).max()),
                                  out.data_ptr(), ops._stream()), "mcl_cluster_scores")
@@ -354,13 +283,13 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
     ks = np.array([e[2] for e in enc], dtype=np.int32)
     if (ks > MAX_DIM).any():
         raise ValueError(f"at most {MAX_DIM} distinct labels per slide, got {ks.tolist()}")
-    dev = _device()
-    x, off = _stack_rows([_take_rows(p, e[0], dev) for p, e in zip(preds, enc)], "preds", dev)
+    dev = device("cluster")
+    x, off = stack_rows([_take_rows(p, e[0], dev) for p, e in zip(preds, enc)], "preds", dev)
     _k_per_segment(ks, np.diff(off))
     z = pca_scores(x, off, n_comps)
     km = kmeans(z, ks, off, seed_rows=seed_rows, n_init=n_init, seed=seed, tol=tol, max_iter=max_iter,
                 segment_base=segment_base)
-    truth = torch.from_numpy(np.concatenate([e[1] for e in enc])).to(dev)
+    truth = upload(np.concatenate([e[1] for e in enc]), dev)
     ari, nmi = cluster_scores(truth, km["labels"], off)
     p_all = km["labels"].cpu().numpy()
     inertia, n_iter, restart = km["inertia"].cpu().numpy(), km["n_iter"].cpu().numpy(), km["restart"].cpu().numpy()
@@ -417,8 +346,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         doc = {"ari": res["ari"], "nmi": res["nmi"], "n_comps": a.n_comps, "n_init": a.n_init, "seed": a.seed,
                "slides": [{k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in s.items()}
                           for s in res["slides"]]}
-        with open(a.json, "w") as fh:
-            json.dump(doc, fh, indent=1)
+        write_json(a.json, doc)
     return 0
 
 

@@ -25,9 +25,6 @@ constexpr int CS_THREADS = 256;
 constexpr int CS_VALUES = 1024;     // label values in [0, 1024)
 constexpr int CS_TABLE = 12288;     // distinct(a) * distinct(b) entries of the contingency table held in LDS
 
-template <typename T>
-__device__ __forceinline__ double ldd(const T* p) { return (double)*p; }
-
 // ------------------------------------------------------------------------------------------------------------- PCA
 // column means: lane = column, the four waves stride over the segment's rows, combined wave 0 + 1 + 2 + 3
 template <typename T>
@@ -202,7 +199,7 @@ __global__ __launch_bounds__(256) void pca_scores_kernel(const T* __restrict__ x
     double a = 0.0;
     for (int g = lane; g < G; g += 64) a = fma(ldd(xr + g) - mu[g], V[(long long)g * C + c], a);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);   // wave_sum(a) written out: a call changes this kernel's code
     if (lane == 0) zr[c] = sg[c] * a;
   }
 }

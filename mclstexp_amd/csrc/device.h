@@ -67,6 +67,10 @@ __device__ __forceinline__ uint4 bn_relu_chunk(uint4 v, const float (&sc)[8], co
   return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
+// an fp32 / fp64 / integer element as fp64: the load of the kernels that take their input in either width
+template <typename T>
+__device__ __forceinline__ double ldd(const T* p) { return (double)*p; }
+
 // ---- lanes
 // number of set bits of ``mask`` below this lane
 __device__ __forceinline__ unsigned lanes_below(unsigned long long mask) {

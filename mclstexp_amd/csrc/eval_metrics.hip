@@ -22,9 +22,6 @@ constexpr int SUM_THREADS = 256;
 constexpr int HEG_SAMPLE = 256;    // genes in the sample that sets the candidate threshold
 constexpr int HEG_CAP = 2048;      // candidates ranked in LDS; more -> ranked against all G means in global memory
 
-template <typename T>
-__device__ __forceinline__ double ld64(const T* p) { return (double)*p; }
-
 // writes r, true_mean and the per-gene mean squared / absolute error (work[s][0][g], work[s][1][g])
 template <typename TP, typename TT>
 __global__ __launch_bounds__(STAT_WAVES * 64) void expr_gene_stats_kernel(
@@ -52,8 +49,8 @@ __global__ __launch_bounds__(STAT_WAVES * 64) void expr_gene_stats_kernel(
 #pragma unroll
     for (int u = 0; u < STAT_UNROLL; ++u) {
       const long long row = min(base + (long long)u * STAT_WAVES, last);
-      pv[u] = ld64(pc + row * ldp);
-      tv[u] = ld64(tc + row * ldt);
+      pv[u] = ldd(pc + row * ldp);
+      tv[u] = ldd(tc + row * ldt);
     }
 #pragma unroll
     for (int u = 0; u < STAT_UNROLL; ++u) {
@@ -94,8 +91,8 @@ __global__ __launch_bounds__(STAT_WAVES * 64) void expr_gene_stats_kernel(
 #pragma unroll
     for (int u = 0; u < STAT_UNROLL; ++u) {
       const long long row = min(base + (long long)u * STAT_WAVES, last);
-      pv[u] = ld64(pc + row * ldp);
-      tv[u] = ld64(tc + row * ldt);
+      pv[u] = ldd(pc + row * ldp);
+      tv[u] = ldd(tc + row * ldt);
     }
 #pragma unroll
     for (int u = 0; u < STAT_UNROLL; ++u) {

@@ -48,12 +48,6 @@ struct SlideSet {  // device-resident arrays, one entry per slide (row_off: S + 
   const long long* row_off;
 };
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ int clamp_col(int c, int ncols) { return c < 0 ? 0 : (c >= ncols ? ncols - 1 : c); }
 
 // ---- order-preserving bit pattern of a double (no NaN): a < b <=> key(a) < key(b), -0.0 just below +0.0
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(LIB_WAVES * 64) void hvg_libsize_kernel(SlideSet sl
       if (g < G) acc[u] += (double)x[clamp_col(map ? map[g] : g, nc)];
     }
   }
-  const double a = wave_sum_d((acc[0] + acc[1]) + (acc[2] + acc[3]));
+  const double a = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
   if (lane == 0) lib[sl.row_off[s] + row] = a;
 }
 
@@ -417,7 +411,7 @@ __global__ __launch_bounds__(256) void expr_matrices_kernel(SlideSet sl, const i
       const T* xr = x + (long long)row * ld;
       for (int k = lane; k < K; k += 64) a += (double)xr[clamp_col(sel[k], nc)];
     }
-    a = wave_sum_d(a);
+    a = wave_sum(a);
     if (lane == 0) fac[r] = a != 0.0 ? (float)((double)rescale / a) : 0.f;  // an empty spot stays all-zero
   }
   __syncthreads();

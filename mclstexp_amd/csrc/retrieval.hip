@@ -276,7 +276,7 @@ __global__ __launch_bounds__(KNN_THREADS) void knn_weighted_average_kernel(
   double tot = 0.0;
   for (int j = tid; j < k; j += KNN_THREADS) tot += (double)wgt[j];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);
+  for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o, 64);   // wave_sum(tot) written out: a call changes this kernel's code
   if (lane == 0) red[wave] = tot;
   __syncthreads();
   tot = 0.0;

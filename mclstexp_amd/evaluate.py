@@ -18,70 +18,30 @@ the HIP library these functions raise ``RuntimeError``.
 from __future__ import annotations
 
 import argparse
-import json
 import math
 import os
 import sys
-from typing import Callable, Dict, List, Optional, Sequence, Tuple, Union
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _arrays, _lib, ops
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, device, empty, load_gene_major, paired_offsets, stack_rows, upload,
+                      write_json)
 from ._lib import check
-
-Tensor = torch.Tensor
-ArrayLike = Union[np.ndarray, Tensor]
 
 # dataset -> (top_k, ord of the distance norm in the weighting)
 PRESETS = {"her2st": (200, 1), "cscc": (600, 2), "10x": (200, 2)}
 N_HEG = 50
 SUMMARY_KEYS = ("heg_pcc", "hvg_pcc", "mse", "mae")
 PRED_FILE = "matched_spot_expression_pred_mclSTExp.npy"
-_DTYPE_CODE = {torch.float32: 0, torch.float64: 1}
-
-
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("mclstexp_amd.evaluate: no GPU available (HIP kernels, no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _as_2d(a: ArrayLike, name: str) -> Tensor:
-    t = a if isinstance(a, Tensor) else torch.as_tensor(np.asarray(a))
-    if t.dim() != 2:
-        raise ValueError(f"{name}: expected a 2-D (spots, genes) array, got shape {tuple(t.shape)}")
-    return t
 
 
 def validate_offsets(offsets: Sequence[int], rows: int) -> np.ndarray:
     """The preconditions of mcl_expr_metrics' device-resident offsets, checked on the host: offsets[0] = 0, every fold
     >= 2 spots (scipy.stats.pearsonr raises below 2), offsets[-1] = rows.  Returns them as int64."""
-    off = np.asarray(offsets)
-    if off.ndim != 1 or off.size < 2 or not np.issubdtype(off.dtype, np.integer):
-        raise ValueError(f"offsets must be a 1-D integer array of S + 1 >= 2 entries, got {off!r}")
-    off = off.astype(np.int64)
-    if off[0] != 0 or off[-1] != rows:
-        raise ValueError(f"offsets must run from 0 to the number of rows ({rows}), got {off[0]} .. {off[-1]}")
-    seg = np.diff(off)
-    if (seg < 2).any():
-        raise ValueError(f"every fold needs >= 2 spots (Pearson r is undefined below 2); fold sizes {seg.tolist()}")
-    return off
-
-
-def _stack(parts: Sequence[ArrayLike], name: str, dev: torch.device) -> Tensor:
-    """The folds row-stacked into one row-major device matrix (no copy for a single row-major device tensor)."""
-    ts = [_as_2d(p, f"{name}[{i}]") for i, p in enumerate(parts)]
-    dtypes = {t.dtype for t in ts}
-    dtype = dtypes.pop() if len(dtypes) == 1 and ts[0].dtype in _DTYPE_CODE else torch.float64
-    if len(ts) == 1 and ts[0].is_cuda and ts[0].dtype == dtype and (ts[0].stride(1) == 1 or ts[0].shape[1] == 1):
-        return ts[0]
-    out = torch.empty((sum(t.shape[0] for t in ts), ts[0].shape[1]), device=dev, dtype=dtype)
-    r = 0
-    for t in ts:
-        out[r:r + t.shape[0]].copy_(t)     # same dtype, contiguous: a plain copy, no compute kernel
-        r += t.shape[0]
-    return out
+    return _arrays.validate_offsets(offsets, rows, min_rows=2, noun="fold")
 
 
 def metrics_device(pred: Tensor, true: Tensor, offsets: Sequence[int], n_heg: int = N_HEG) -> Dict[str, Tensor]:
@@ -96,37 +56,35 @@ def metrics_device(pred: Tensor, true: Tensor, offsets: Sequence[int], n_heg: in
     if n_heg < 1:
         raise ValueError("n_heg must be >= 1")
     for t, name in ((pred, "pred"), (true, "true")):
-        if not t.is_cuda or t.dtype not in _DTYPE_CODE or (t.stride(1) != 1 and G != 1):
+        if not t.is_cuda or t.dtype not in FLOAT_CODE or (t.stride(1) != 1 and G != 1):
             raise RuntimeError(f"{name}: expected a row-major float32 / float64 device matrix")
-    dev = pred.device
-    off_d = torch.from_numpy(off).to(dev)
-    r = torch.empty((S, G), device=dev, dtype=torch.float64)
-    true_mean = torch.empty((S, G), device=dev, dtype=torch.float64)
-    heg = torch.empty((S, n_heg), device=dev, dtype=torch.int64)
-    summary = torch.empty((S, 5), device=dev, dtype=torch.float64)
-    work = torch.empty((2 * S * G,), device=dev, dtype=torch.float64)
-    check(_lib.lib().mcl_expr_metrics(pred.data_ptr(), pred.stride(0), _DTYPE_CODE[pred.dtype], true.data_ptr(),
-                                      true.stride(0), _DTYPE_CODE[true.dtype], off_d.data_ptr(), S, G, n_heg,
+    off_d = upload(off, pred.device)
+    e = empty(pred.device)
+    r, true_mean, summary = e((S, G), torch.float64), e((S, G), torch.float64), e((S, 5), torch.float64)
+    heg = e((S, n_heg), torch.int64)
+    work = e((2 * S * G,), torch.float64)
+    check(_lib.lib().mcl_expr_metrics(pred.data_ptr(), pred.stride(0), FLOAT_CODE[pred.dtype], true.data_ptr(),
+                                      true.stride(0), FLOAT_CODE[true.dtype], off_d.data_ptr(), S, G, n_heg,
                                       r.data_ptr(), true_mean.data_ptr(), heg.data_ptr(), summary.data_ptr(),
                                       work.data_ptr(), ops._stream()), "mcl_expr_metrics")
     return {"r": r, "true_mean": true_mean, "heg": heg, "summary": summary}
+
+
+def stacked_metrics(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike], offsets: np.ndarray,
+                    n_heg: int = N_HEG) -> Dict[str, Tensor]:
+    """``metrics_device`` of the per-fold arrays row-stacked on the device (``offsets``: their ``paired_offsets``).  Device
+    folds of differing dtype are converted by the stacking copy."""
+    dev = device("evaluate")
+    return metrics_device(stack_rows(preds, "preds", dev, convert_on_device=True)[0],
+                          stack_rows(trues, "trues", dev, convert_on_device=True)[0], offsets, n_heg)
 
 
 def score_folds(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike], n_heg: int = N_HEG) -> Dict[str, object]:
     """Scores every fold's (spots, genes) prediction against its ground truth in ONE metrics call.  Returns
     ``folds``: per-fold dicts as ``score`` returns them, and ``heg_pcc``, ``hvg_pcc``, ``mse``, ``mae``: ``np.mean`` over
     the folds, as the reference's scripts print them (a NaN fold heg_pcc makes the average NaN)."""
-    if len(preds) != len(trues) or not preds:
-        raise ValueError(f"need one ground truth per prediction and >= 1 fold; got {len(preds)} and {len(trues)}")
-    for i, (p, t) in enumerate(zip(preds, trues)):
-        if tuple(p.shape) != tuple(t.shape):
-            raise ValueError(f"fold {i}: pred {tuple(p.shape)} and true {tuple(t.shape)} differ in shape")
-        if p.ndim != 2 or p.shape[1] != preds[0].shape[1]:
-            raise ValueError(f"fold {i}: expected (spots, {preds[0].shape[1]}) arrays, got {tuple(p.shape)}")
-    offsets = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in preds])]).astype(np.int64)
-    validate_offsets(offsets, int(offsets[-1]))
-    dev = _device()
-    m = metrics_device(_stack(preds, "preds", dev), _stack(trues, "trues", dev), offsets, n_heg)
+    offsets = paired_offsets(preds, trues, "fold")
+    m = stacked_metrics(preds, trues, offsets, n_heg)
     r, heg, summ = m["r"].cpu().numpy(), m["heg"].cpu().numpy(), m["summary"].cpu().numpy()
     folds = [{"heg_pcc": float(summ[s, 0]), "hvg_pcc": float(summ[s, 1]), "mse": float(summ[s, 2]),
               "mae": float(summ[s, 3]), "n_valid": int(summ[s, 4]), "pcc": r[s], "heg_genes": heg[s]}
@@ -151,8 +109,8 @@ def gene_pcc(pred: ArrayLike, true: ArrayLike) -> np.ndarray:
 def _predict_device(spot_key: ArrayLike, expression_key: ArrayLike, image_query: ArrayLike, top_k: int,
                     ord: int) -> Tensor:
     from . import retrieval
-    key = retrieval._to_dev(spot_key, "spot_key")
-    qry = retrieval._to_dev(image_query, "image_query")
+    key = retrieval.to_device(spot_key, "spot_key")
+    qry = retrieval.to_device(image_query, "image_query")
     _, idx = retrieval.find_matches_device(key, qry, top_k)
     _, expr = retrieval.weighted_average_device(key, expression_key, qry, idx, ord)
     return expr
@@ -167,7 +125,7 @@ def evaluate_fold(spot_key: ArrayLike, expression_key: ArrayLike, image_query: A
 
 def _cat_rows(parts: Sequence[ArrayLike]) -> ArrayLike:
     if any(isinstance(p, Tensor) for p in parts):
-        dev = _device()
+        dev = device("evaluate")
         return torch.cat([torch.as_tensor(p).to(device=dev, dtype=torch.float32) for p in parts])
     return np.concatenate([np.asarray(p, dtype=np.float32) for p in parts])
 
@@ -232,11 +190,7 @@ def load_fold_embeddings(embedding_dir: str, fold: int, n_slides: int) -> Tuple[
 
 def load_expressions(paths: Sequence[str]) -> List[np.ndarray]:
     """(N_i, G) arrays from preprocessed_matrix.npy files stored (G, N_i)."""
-    ex = [np.load(p).T for p in paths]
-    for p, e in zip(paths, ex):
-        if e.ndim != 2 or e.shape[1] != ex[0].shape[1]:
-            raise ValueError(f"{p}: expected (G, N) with G = {ex[0].shape[1]}, got {e.T.shape}")
-    return ex
+    return load_gene_major(paths)
 
 
 def check_layout(images: Sequence[Optional[np.ndarray]], spots: Sequence[np.ndarray], expressions: Sequence[np.ndarray],
@@ -300,8 +254,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         doc = {k: _json_value(res[k]) for k in SUMMARY_KEYS}
         doc.update(dataset=args.dataset, top_k=top_k, ord=ord_,
                    folds=[{k: _json_value(v) for k, v in f.items()} for f in res["folds"]])
-        with open(args.json, "w") as fh:
-            json.dump(doc, fh, indent=1)
+        write_json(args.json, doc)
     return 0
 
 

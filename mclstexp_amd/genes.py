@@ -25,26 +25,25 @@ import numpy as np
 import torch
 
 from . import _lib, evaluate, ops
+from ._arrays import ArrayLike, Tensor, device, empty, load_gene_major, matrix, paired_offsets, upload
 from ._lib import check
-from .evaluate import ArrayLike, Tensor
 
 TOP_N = 7
 PRED_FILE = evaluate.PRED_FILE     # what the tutorial reads per slide; ``evaluate --save_pred`` writes it
 
 
 def _f64_matrix(a: ArrayLike, name: str, dev: torch.device) -> Tensor:
-    t = a if isinstance(a, Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
-    if t.dim() != 2 or t.dtype != torch.float64:
-        raise ValueError(f"{name}: expected a 2-D (slides, genes) float64 array, got {tuple(t.shape)} {t.dtype}")
-    t = t.to(dev)
-    return t if t.is_contiguous() else t.contiguous()    # (a contiguous copy is a copy kernel of the runtime's)
+    """A dense (slides, genes) float64 device matrix: arrays are converted on the host, tensors must be float64."""
+    if isinstance(a, Tensor) and a.dtype != torch.float64:
+        raise ValueError(f"{name}: expected a float64 tensor, got {a.dtype}")
+    return matrix(a, name, dev, (torch.float64,), torch.float64, dense=True)
 
 
 def pvalues_device(r: Tensor, offsets: Sequence[int]) -> Tuple[Tensor, Tensor]:
     """One ``mcl_pearson_pvalue`` call: ``r`` (S, G) float64 on the device (``evaluate.metrics_device(...)["r"]``),
     ``offsets`` the S + 1 fold boundaries that produced it (host integers, or a device int64 tensor).  Returns the
     device tensors ``p`` and ``neglog10p``, both (S, G) float64."""
-    evaluate._device()
+    device("genes")
     if not isinstance(r, Tensor) or not r.is_cuda or r.dtype != torch.float64 or r.dim() != 2 or not r.is_contiguous():
         raise RuntimeError("r: expected a contiguous (slides, genes) float64 device matrix")
     S, G = r.shape
@@ -54,35 +53,22 @@ def pvalues_device(r: Tensor, offsets: Sequence[int]) -> Tuple[Tensor, Tensor]:
         off_d = offsets.to(r.device).contiguous()
     else:
         off = np.asarray(offsets)
-        if off.ndim != 1 or off.size != S + 1 or not np.issubdtype(off.dtype, np.integer):
+        if off.ndim != 1 or off.size != S + 1:
             raise ValueError(f"offsets must be a 1-D integer array of S + 1 = {S + 1} entries, got {off!r}")
-        off = evaluate.validate_offsets(off, int(off[-1]))
-        off_d = torch.from_numpy(off).to(r.device)
-    p = torch.empty((S, G), device=r.device, dtype=torch.float64)
-    nl = torch.empty((S, G), device=r.device, dtype=torch.float64)
+        off_d = upload(evaluate.validate_offsets(off, off[-1]), r.device)
+    e = empty(r.device)
+    p, nl = e((S, G), torch.float64), e((S, G), torch.float64)
     check(_lib.lib().mcl_pearson_pvalue(r.data_ptr(), off_d.data_ptr(), S, G, p.data_ptr(), nl.data_ptr(),
                                         ops._stream()), "mcl_pearson_pvalue")
     return p, nl
 
 
-def _check_slides(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike]) -> np.ndarray:
-    if len(preds) != len(trues) or not preds:
-        raise ValueError(f"need one ground truth per prediction and >= 1 slide; got {len(preds)} and {len(trues)}")
-    for i, (p, t) in enumerate(zip(preds, trues)):
-        if tuple(p.shape) != tuple(t.shape):
-            raise ValueError(f"slide {i}: pred {tuple(p.shape)} and true {tuple(t.shape)} differ in shape")
-        if p.ndim != 2 or p.shape[1] != preds[0].shape[1]:
-            raise ValueError(f"slide {i}: expected (spots, {preds[0].shape[1]}) arrays, got {tuple(p.shape)}")
-    offsets = np.concatenate([[0], np.cumsum([int(p.shape[0]) for p in preds])]).astype(np.int64)
-    return evaluate.validate_offsets(offsets, int(offsets[-1]))
-
-
 def significance_device(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike]) -> Dict[str, Tensor]:
     """``pcc``, ``p``, ``neglog10p`` as (S, G) float64 device tensors: one ``evaluate.metrics_device`` call for r, one
     ``mcl_pearson_pvalue`` call on it; nothing leaves the device in between."""
-    offsets = _check_slides(preds, trues)
-    dev = evaluate._device()
-    m = evaluate.metrics_device(evaluate._stack(preds, "preds", dev), evaluate._stack(trues, "trues", dev), offsets)
+    offsets = paired_offsets(preds, trues, "slide")
+    device("genes")                                   # without a GPU this module is the one that says so
+    m = evaluate.stacked_metrics(preds, trues, offsets)
     p, nl = pvalues_device(m["r"], offsets)
     return {"pcc": m["r"], "p": p, "neglog10p": nl}
 
@@ -108,7 +94,7 @@ def rank_genes(neglog10p: ArrayLike, r: ArrayLike, top_n: int = TOP_N, log_space
     underflowed.  On slides of a few thousand spots that happens to every well-predicted gene (n = 4784: from r ~ 0.5
     on), all of them then share the mean ``inf`` and the ranking among them is arbitrary -- which is why it is not the
     default.  Where no ``p`` underflows (the HER2ST slides) the two modes agree to rounding."""
-    dev = evaluate._device()
+    dev = device("genes")
     if not log_space:
         if p is None:
             raise ValueError("log_space=False ranks by -log10 of the fp64 p: pass p")
@@ -121,12 +107,9 @@ def rank_genes(neglog10p: ArrayLike, r: ArrayLike, top_n: int = TOP_N, log_space
         raise ValueError(f"neglog10p {tuple(nl.shape)} and r {tuple(rr.shape)} differ in shape")
     S, G = nl.shape
     top_n = max(1, min(int(top_n), G))
-    mean = torch.empty((G,), device=dev, dtype=torch.float64)
-    n_defined = torch.empty((G,), device=dev, dtype=torch.int32)
-    order = torch.empty((G,), device=dev, dtype=torch.int64)
-    best_slide = torch.empty((G,), device=dev, dtype=torch.int32)
-    best_value = torch.empty((G,), device=dev, dtype=torch.float64)
-    best_r = torch.empty((G,), device=dev, dtype=torch.float64)
+    e = empty(dev)
+    mean, best_value, best_r = e((G,), torch.float64), e((G,), torch.float64), e((G,), torch.float64)
+    n_defined, best_slide, order = e((G,), torch.int32), e((G,), torch.int32), e((G,), torch.int64)
     check(_lib.lib().mcl_gene_rank(nl.data_ptr(), rr.data_ptr(), S, G, top_n, mean.data_ptr(), n_defined.data_ptr(),
                                    order.data_ptr(), best_slide.data_ptr(), best_value.data_ptr(), best_r.data_ptr(),
                                    ops._stream()), "mcl_gene_rank")
@@ -187,14 +170,11 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
 
 def load_slides(pred_paths: Sequence[str], true_paths: Sequence[str]) -> Tuple[List[np.ndarray], List[np.ndarray]]:
     """(spots, genes) arrays from files stored (G, N_i), the layout the reference stores; shapes checked pairwise."""
-    preds = [np.load(f) for f in pred_paths]
-    trues = [np.load(f) for f in true_paths]
+    preds, trues = load_gene_major(pred_paths), load_gene_major(true_paths)
     for fp, ft, a, b in zip(pred_paths, true_paths, preds, trues):
-        if a.ndim != 2 or a.shape[0] != preds[0].shape[0]:
-            raise ValueError(f"{fp}: expected (G, N) with G = {preds[0].shape[0]}, got {a.shape}")
         if b.shape != a.shape:
-            raise ValueError(f"{ft}: expected {a.shape} as {fp}, got {b.shape}")
-    return [a.T for a in preds], [b.T for b in trues]
+            raise ValueError(f"{ft}: expected {a.T.shape} as {fp}, got {b.T.shape}")
+    return preds, trues
 
 
 def load_gene_names(path: Optional[str], G: int) -> Optional[List[str]]:

@@ -27,19 +27,16 @@ HIP library these functions raise ``RuntimeError``.
 from __future__ import annotations
 
 import argparse
-import json
 import os
 import sys
-from typing import Dict, List, Optional, Sequence, Tuple, Union
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload, write_json
 from ._lib import check
-
-Tensor = torch.Tensor
-ArrayLike = Union[np.ndarray, Tensor]
 
 N_TOP_GENES = 1000       # hvg_her2st.py:24
 MAX_ROWS = 50000         # spots per slide (as mclstexp_amd.cluster)
@@ -50,12 +47,6 @@ _DTYPE_CODE = {torch.float32: 0, torch.int32: 1}
 STATUS_TEXT = {1: "the gene means are all equal (or not finite): pandas.cut's special case is not reproduced",
                2: "no spot holds a count", 4: "no gene has a defined normalised dispersion",
                8: "a column map entry lies outside the slide's columns"}
-
-
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("mclstexp_amd.preprocess: no GPU available (HIP kernels, no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
 
 
 # ------------------------------------------------------------------------------------------------- host bookkeeping
@@ -104,27 +95,13 @@ def shared_genes(name_lists: Sequence[Sequence[str]]) -> Tuple[List[str], List[n
 # ------------------------------------------------------------------------------------------------------ slide sets
 def _slide(x: ArrayLike, name: str, dev: torch.device, dtype: Optional[torch.dtype] = None) -> Tensor:
     """A row-major float32 / int32 device matrix (no copy when it already is one).  Host arrays of other dtypes are
-    converted on the host: integers to int32, everything else to float32."""
-    t = x if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x))
-    if t.dim() != 2:
-        raise ValueError(f"{name}: expected a 2-D (spots, genes) count matrix, got shape {tuple(t.shape)}")
-    want = dtype
-    if want is None:
-        want = t.dtype if t.dtype in _DTYPE_CODE else (
-            torch.float32 if (t.dtype.is_floating_point or t.dtype == torch.bool) else torch.int32)
-    if t.dtype != want:
-        if t.is_cuda:
-            raise ValueError(f"{name}: device slides must be float32 or int32 and share one dtype, got {t.dtype}")
+    converted on the host: integers to int32, everything else to float32.  ``dtype``: the one dtype to end up with."""
+    def host_dtype(t: Tensor) -> torch.dtype:
+        want = dtype or (torch.float32 if (t.dtype.is_floating_point or t.dtype == torch.bool) else torch.int32)
         if want == torch.int32 and t.numel() and (int(t.max()) > 2 ** 31 - 1 or int(t.min()) < -2 ** 31):
             raise ValueError(f"{name}: counts do not fit int32")
-        t = t.to(want)
-    if t.is_cuda and (t.stride(1) == 1 or t.shape[1] == 1) and t.stride(0) >= t.shape[1]:
-        return t
-    if t.is_cuda:
-        out = torch.empty(tuple(t.shape), device=dev, dtype=t.dtype)
-        out.copy_(t)
-        return out
-    return t.contiguous().to(dev)
+        return want
+    return matrix(x, name, dev, (dtype,) if dtype is not None else _DTYPE_CODE, host_dtype)
 
 
 def _check_shapes(slides: Sequence[ArrayLike]) -> np.ndarray:
@@ -164,11 +141,11 @@ class _SlideSet:
         self.S = len(self.tensors)
         self.rows = np.array([t.shape[0] for t in self.tensors], dtype=np.int32)
         self.ncols = np.array([t.shape[1] for t in self.tensors], dtype=np.int32)
-        self.row_off = np.concatenate([[0], np.cumsum(self.rows.astype(np.int64))]).astype(np.int64)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
-        self.d_ptr = up(np.array([t.data_ptr() for t in self.tensors], dtype=np.int64))
-        self.d_ld = up(np.array([t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in self.tensors], dtype=np.int64))
-        self.d_rows, self.d_ncols, self.d_row_off = up(self.rows), up(self.ncols), up(self.row_off)
+        self.row_off = cumulative_offsets(self.rows)
+        self.d_ptr = upload(np.array([t.data_ptr() for t in self.tensors], dtype=np.int64), dev)
+        self.d_ld = upload(np.array([t.stride(0) if t.shape[0] > 1 else t.shape[1] for t in self.tensors], dtype=np.int64),
+                           dev)
+        self.d_rows, self.d_ncols, self.d_row_off = (upload(a, dev) for a in (self.rows, self.ncols, self.row_off))
         self.dev = dev
 
     def args(self):
@@ -218,12 +195,12 @@ def gene_stats(slides: Sequence[ArrayLike], colmaps: Optional[Sequence[Optional[
     ``highly_variable`` (S, G) bool, ``cutoff``, ``target_sum`` (S,) fp64.  One read-back (the per-slide status word):
     a slide whose gene means are all equal, that holds no count or no defined dispersion raises ``ValueError``."""
     n_top_genes, cm, G = _stats_args(slides, colmaps, n_top_genes)
-    dev = _device()
+    dev = device("preprocess")
     lib = _lib.lib()
     ss = _SlideSet(slides, dev)
     S = ss.S
-    cm_d = torch.from_numpy(cm).to(dev) if cm is not None else None
-    e = lambda shape, dt: torch.empty(shape, device=dev, dtype=dt)  # noqa: E731
+    cm_d = upload(cm, dev) if cm is not None else None
+    e = empty(dev)
     res = {"means": e((S, G), torch.float64), "dispersions": e((S, G), torch.float64),
            "dispersions_norm": e((S, G), torch.float64), "mean_bin": e((S, G), torch.int32),
            "highly_variable": e((S, G), torch.bool), "cutoff": e((S,), torch.float64),
@@ -257,12 +234,11 @@ def pool(highly_variable: ArrayLike, extra: Optional[ArrayLike] = None) -> Tuple
         if ex.size and (ex.min() < 0 or ex.max() >= G):
             raise ValueError(f"extra: gene indices must lie in 0 .. {G - 1}")
         ex = ex.astype(np.int32)
-    dev = _device()
+    dev = device("preprocess")
     lib = _lib.lib()
     hv = hv.to(dev).contiguous()
-    ex_d = torch.from_numpy(ex).to(dev) if ex is not None and ex.size else None
-    uni = torch.empty((G,), device=dev, dtype=torch.bool)
-    inter = torch.empty((G,), device=dev, dtype=torch.bool)
+    ex_d = upload(ex, dev) if ex is not None and ex.size else None
+    uni, inter = torch.empty((G,), device=dev, dtype=torch.bool), torch.empty((G,), device=dev, dtype=torch.bool)
     check(lib.mcl_hvg_pool(hv.data_ptr(), S, G, ops._p(ex_d), int(ex.size) if ex_d is not None else 0, uni.data_ptr(),
                            inter.data_ptr(), ops._stream()), "mcl_hvg_pool")
     return uni, inter
@@ -283,10 +259,10 @@ def expression_matrices(slides: Sequence[ArrayLike], colmaps: Optional[Sequence[
         raise ValueError(f"genes: indices must lie in 0 .. {G - 1}")
     S, K = len(slides), int(g.size)
     sel = cm[:, g] if cm is not None else np.broadcast_to(g.astype(np.int32), (S, K))
-    dev = _device()
+    dev = device("preprocess")
     lib = _lib.lib()
     ss = _SlideSet(slides, dev)
-    sel_d = torch.from_numpy(np.array(sel, dtype=np.int32, order="C")).to(dev)
+    sel_d = upload(np.asarray(sel, dtype=np.int32), dev)
     out = torch.empty((K * int(ss.row_off[-1]),), device=dev, dtype=torch.float32)
     check(lib.mcl_expression_matrices(*ss.args(), sel_d.data_ptr(), S, K, int(ss.rows.max()), float(RESCALE),
                                       out.data_ptr(), ops._stream()), "mcl_expression_matrices")
@@ -335,7 +311,7 @@ def run(slides: Sequence[ArrayLike], names: Optional[Sequence[Sequence[str]]] = 
         shared, colmaps = shared_genes(names)
     _, _, G = _stats_args(slides, colmaps, n_top_genes)
     forced = _gene_indices(gene_list, shared, G) if gene_list is not None else None
-    tensors = _SlideSet(slides, _device()).tensors          # one upload for both calls
+    tensors = _SlideSet(slides, device("preprocess")).tensors          # one upload for both calls
     stats = gene_stats(tensors, colmaps, n_top_genes)
     uni, inter = pool(stats["highly_variable"])
     n_union, n_inter = int(uni.cpu().numpy().sum()), int(inter.cpu().numpy().sum())
@@ -421,8 +397,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                "slides": [slide_name(f) for f in a.counts],
                "cutoff": res["stats"]["cutoff"].cpu().numpy().tolist(),
                "target_sum": res["stats"]["target_sum"].cpu().numpy().tolist()}
-        with open(a.json, "w") as fh:
-            json.dump(doc, fh, indent=1)
+        write_json(a.json, doc)
     return 0
 
 

@@ -16,35 +16,26 @@ threshold missed).  No CPU fallback: without a GPU / the HIP library these funct
 """
 from __future__ import annotations
 
-from typing import Dict, Iterable, Optional, Tuple, Union
+from typing import Dict, Iterable, Optional, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib, ops
+from ._arrays import ArrayLike, Tensor, device, matrix
 from ._lib import check
-
-Tensor = torch.Tensor
-ArrayLike = Union[np.ndarray, Tensor]
 
 # upper bound of the (Q_chunk, N) fp32 similarity workspace
 SIM_WORKSPACE_BYTES = 1 << 30
 
 
-def _device() -> torch.device:
-    if not torch.cuda.is_available():
-        raise RuntimeError("mclstexp_amd.retrieval: no GPU available (HIP kernels, no CPU fallback)")
-    return torch.device("cuda", torch.cuda.current_device())
-
-
-def _to_dev(a: ArrayLike, name: str) -> Tensor:
+def to_device(a: ArrayLike, name: str) -> Tensor:
+    """``a`` as a row-major float32 device matrix (itself when it already is one).  A host array is uploaded as it lies
+    in memory -- a transposed view is transposed by the device copy, not on the host -- and converted on the device."""
     t = torch.as_tensor(a) if not isinstance(a, Tensor) else a
-    if t.dim() != 2:
-        raise RuntimeError(f"{name}: expected a 2-D array, got shape {tuple(t.shape)}")
     if not t.is_cuda:
-        t = t.to(_device(), non_blocking=False)
-    t = t.to(torch.float32)
-    return ops._rowmajor(t, name)
+        t = t.to(device("retrieval"), non_blocking=False)
+    return matrix(t.to(torch.float32), name, t.device, (torch.float32,), torch.float32, RuntimeError)
 
 
 def l2_normalize(x: Tensor) -> Tensor:
@@ -152,8 +143,8 @@ def find_matches_filtered(query: Tensor, keys: Tensor, top_k: int) -> Tuple[Tens
 def find_matches_device(spot_embeddings: ArrayLike, query_embeddings: ArrayLike, top_k: int = 1
                         ) -> Tuple[Tensor, Tensor]:
     """(values, indices) as device tensors, shapes (Q, top_k): cosine top-k of every query against all keys."""
-    keys = l2_normalize(_to_dev(spot_embeddings, "spot_embeddings"))
-    query = l2_normalize(_to_dev(query_embeddings, "query_embeddings"))
+    keys = l2_normalize(to_device(spot_embeddings, "spot_embeddings"))
+    query = l2_normalize(to_device(query_embeddings, "query_embeddings"))
     if keys.shape[1] != query.shape[1]:
         raise RuntimeError(f"embedding widths differ: keys {tuple(keys.shape)}, queries {tuple(query.shape)}")
     q, n = query.shape[0], keys.shape[0]
@@ -186,8 +177,8 @@ def weighted_average_device(spot_key: ArrayLike, expression_key: Optional[ArrayL
     """The reference's per-query weighting loop for all queries at once (device tensors, fp32):
     ``a = ||spot_key[idx] - query||_ord``, ``w = a**-2 / sum(a**-2)``, np.average of the matched embeddings and
     expression rows.  ``ord=1``: evel_her2st.py:176; ``ord=2``: evel_cscc.py:209, evel_visium.py:197."""
-    key = _to_dev(spot_key, "spot_key")
-    qry = _to_dev(image_query, "image_query")
+    key = to_device(spot_key, "spot_key")
+    qry = to_device(image_query, "image_query")
     idx = torch.as_tensor(indices)
     if idx.dim() != 2 or idx.shape[0] != qry.shape[0]:
         raise RuntimeError(f"indices must be (Q, k); got {tuple(idx.shape)} for {qry.shape[0]} queries")
@@ -199,7 +190,7 @@ def weighted_average_device(spot_key: ArrayLike, expression_key: Optional[ArrayL
     expr_t = expr_out = None
     genes = 0
     if expression_key is not None:
-        expr_t = _to_dev(expression_key, "expression_key")
+        expr_t = to_device(expression_key, "expression_key")
         if expr_t.shape[0] != key.shape[0]:
             raise RuntimeError("expression_key and spot_key must have one row per training spot")
         genes = expr_t.shape[1]
@@ -219,8 +210,8 @@ def predict_expression(spot_key: ArrayLike, expression_key: ArrayLike, image_que
     reference's ``np.zeros`` buffers."""
     if method != "weighted":
         raise ValueError("only the reference's active method 'weighted' is implemented")
-    key = _to_dev(spot_key, "spot_key")
-    qry = _to_dev(image_query, "image_query")
+    key = to_device(spot_key, "spot_key")
+    qry = to_device(image_query, "image_query")
     _, idx = find_matches_device(key, qry, top_k)
     emb, expr = weighted_average_device(key, expression_key, qry, idx, ord)
     return {"indices": idx.cpu().numpy(),

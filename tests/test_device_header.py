@@ -27,7 +27,7 @@ def defined_names(text):
 def test_device_header_defines_the_shared_helpers():
     names = defined_names(open(os.path.join(CSRC, "device.h")).read())
     for n in ("bf16_t", "bf16x2_t", "bf16x8", "v4s", "f32x2", "f32x4", "f32x16", "u32x2", "u32x4", "u64", "bf_lo",
-              "bf_hi", "bf2f", "pack_bf16", "f2bf", "round_bf16", "pack8", "unpack8", "lanes_below", "half_wave_sum",
+              "bf_hi", "bf2f", "pack_bf16", "f2bf", "round_bf16", "pack8", "unpack8", "ldd", "lanes_below", "half_wave_sum",
               "opaque_lane", "glds16", "glds16s", "glds4", "buffer_lds16", "bn_relu_chunk", "MCL_LDSP", "MCL_GLBP"):
         assert n in names, n
     assert '#include "device.h"' in open(os.path.join(CSRC, "common.h")).read()
