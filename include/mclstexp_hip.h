@@ -843,6 +843,50 @@ int mcl_gene_rank(const double* neglog10p, const double* r, int32_t S, int32_t G
                   int32_t* n_defined, int64_t* order, int32_t* best_slide, double* best_value, double* best_r,
                   mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- BLEEP's prediction methods and scoring protocol
+ * (csrc/bleep_eval.hip; added under ABI 13: new entry points only).  baselines/Bleep/BLEEP_inference.ipynb, cell 5 (the
+ * three prediction methods and the scoring block) and cell 7 (the gene-gene-correlation matrices).  No floating-point
+ * atomics; every reduction order depends only on the problem's own shape, so a segment scored inside a batch is
+ * bit-identical to the same segment scored alone.
+ *
+ * mcl_knn_combine: arguments, NULL rules and the k * 8 <= 60000 limit of mcl_knn_weighted_average; fp32 in and out.  Per
+ *   query i with neighbours idx = indices[i,:], by mode:
+ *     0 FIRST      emb_pred[i,:] = spot_key[idx_0,:], expr_pred[i,:] = expression_key[idx_0,:], bit for bit (method "simple");
+ *     1 MEAN       np.average(rows idx, axis=0)                                                  (method "average");
+ *     2 BLEEP_EXP  d_j = sum_c (spot_key[idx_j,c] - query[i,c])^2, w_j = exp(-(d_j - d_0 + 1)), np.average(rows idx, axis=0,
+ *                  weights=w) (method "weighted_average").  d_0 belongs to the best COSINE match, not to the nearest
+ *                  neighbour, so an exponent can be positive; w_0 = exp(-1) keeps the weight sum above zero.
+ *   d_j, the weights, their sum and the column sums are fp64 (the notebook: fp32 distances and weights); the result is
+ *   rounded to fp32 once.  Any other mode: MCL_EUNSUPPORTED.  Rows are read with 16-byte loads where the matrix's base is
+ *   16-byte aligned and its leading dimension a multiple of 4, else element by element.
+ * mcl_cell_pearson: r_cell[i] = Pearson r of pred[i,:] against truth[i,:] over the G genes (np.corrcoef(...)[0, 1]) for
+ *   every row: two passes, fp64; NaN when either row is exactly constant, otherwise clipped to [-1, 1].  dtype codes as in
+ *   mcl_expr_metrics.  rows == 0 is MCL_OK.
+ * mcl_bleep_summary: truth (rows x G), offsets[S + 1] device-resident as in mcl_expr_metrics, r_gene (S x G) as
+ *   mcl_expr_metrics writes it, r_cell (rows) as mcl_cell_pearson writes it, markers: n_markers device int32 gene indices in
+ *   [0, G) (the caller checks them; NULL when n_markers == 0).  Per segment s:
+ *     gene_sum[S x G], gene_var[S x G]   np.sum / np.var (population variance) of the truth's columns, two passes, fp64;
+ *     top_sum, top_var [S x n_top] int64  the n_top genes of largest sum / variance, best first, exact rank by counting, equal
+ *                                        values to the HIGHER gene index first: np.argsort(kind="stable")[-n_top:][::-1];
+ *     summary[S x 7]   { cell_mean = mean of the segment's non-NaN r_cell (NaN if none), n_cells_valid, n_genes_valid = the
+ *                      number of non-NaN r_gene, max_r over them (NaN if none), heg_mean = mean of r_gene over top_sum (NaN
+ *                      propagates, np.mean), hvg_mean = the same over top_var, marker_mean = the same over markers (NaN when
+ *                      n_markers == 0) }.
+ *   1 <= n_top <= G; S <= 65535 and G <= 1048576, MCL_EUNSUPPORTED beyond.  S == 0 is MCL_OK.
+ * mcl_corr_from_gram: gram (m x m, row-major, dense) = a centred Gram matrix Xc^T Xc as mcl_pca_gram writes its primal form;
+ *   corr[i,j] = gram[i,j] / sqrt(gram[i,i]) / sqrt(gram[j,j]) clipped to [-1, 1] (np.corrcoef), NaN where gram[i,i] or
+ *   gram[j,j] is 0 (a constant column).  m <= 32768.                                                                 */
+int mcl_knn_combine(const float* spot_key, int64_t ldk, const float* expression_key, int64_t lde, const float* query,
+                    int64_t ldq, const int64_t* indices, int32_t n_query, int32_t k, int32_t dim, int32_t genes,
+                    int32_t mode, float* emb_pred, float* expr_pred, mcl_stream_t stream);
+int mcl_cell_pearson(const void* pred, int64_t ld_pred, int32_t pred_dtype, const void* truth, int64_t ld_true,
+                     int32_t true_dtype, int64_t rows, int32_t G, double* r_cell, mcl_stream_t stream);
+int mcl_bleep_summary(const void* truth, int64_t ld_true, int32_t true_dtype, const int64_t* offsets, int32_t S, int32_t G,
+                      int32_t n_top, const double* r_gene, const double* r_cell, const int32_t* markers, int32_t n_markers,
+                      double* gene_sum, double* gene_var, int64_t* top_sum, int64_t* top_var, double* summary,
+                      mcl_stream_t stream);
+int mcl_corr_from_gram(const double* gram, int32_t m, double* corr, mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- spatial-domain clustering (ABI 12; csrc/cluster.hip)
  * The reference's cluster() (utils.py:67-79): PCA -> k-means -> ARI / NMI against given labels, for S slides per call.
  * Common contract: row-stacked row-major device matrices, offsets[S + 1] device-resident int64 with offsets[0] = 0, every

@@ -214,6 +214,10 @@ PROTOTYPES = {
     "mcl_expr_metrics": [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_pearson_pvalue": [c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "mcl_gene_rank": [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_knn_combine": [c_p, c_l, c_p, c_l, c_p, c_l, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "mcl_cell_pearson": [c_p, c_l, c_i, c_p, c_l, c_i, c_l, c_i, c_p, c_p],
+    "mcl_bleep_summary": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_corr_from_gram": [c_p, c_i, c_p, c_p],
     "mcl_pca_gram": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     "mcl_pca_project": [c_p, c_l, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_kmeans": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, C.c_uint64, c_i, c_d, c_i, c_p, c_p, c_p, c_p, c_p, c_p,

@@ -202,18 +202,60 @@ def weighted_average_device(spot_key: ArrayLike, expression_key: Optional[ArrayL
     return emb, expr_out
 
 
+# BLEEP's three prediction methods (baselines/Bleep/BLEEP_inference.ipynb, cell 5) -> mcl_knn_combine's mode
+COMBINE_MODES = {"simple": 0, "average": 1, "weighted_average": 2}
+
+
+def combine_device(spot_key: ArrayLike, expression_key: Optional[ArrayLike], image_query: ArrayLike, indices: ArrayLike,
+                   method: str) -> Tuple[Tensor, Optional[Tensor]]:
+    """BLEEP's prediction from given matches for all queries at once (device tensors, fp32): ``"simple"`` the rows of the
+    first match, bit for bit; ``"average"`` ``np.average`` of the matched rows; ``"weighted_average"`` the same with
+    ``w_j = exp(-(d_j - d_0 + 1))``, ``d_j = sum((spot_key[idx_j] - query)**2)`` -- distances, weights and sums in fp64 on
+    the device (the notebook's are fp32).  Returns (embeddings (Q, P), expression (Q, G) or None)."""
+    if method not in COMBINE_MODES:
+        raise ValueError(f"method must be one of {sorted(COMBINE_MODES)}, got {method!r}")
+    key = to_device(spot_key, "spot_key")
+    qry = to_device(image_query, "image_query")
+    idx = torch.as_tensor(indices)
+    if idx.dim() != 2 or idx.shape[0] != qry.shape[0]:
+        raise RuntimeError(f"indices must be (Q, k); got {tuple(idx.shape)} for {qry.shape[0]} queries")
+    idx = idx.to(device=key.device, dtype=torch.int64).contiguous()
+    if idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= key.shape[0]):
+        raise IndexError("neighbour index out of range")
+    q, k = idx.shape
+    emb = torch.empty((q, key.shape[1]), device=key.device, dtype=torch.float32)
+    expr_t = expr_out = None
+    genes = 0
+    if expression_key is not None:
+        expr_t = to_device(expression_key, "expression_key")
+        if expr_t.shape[0] != key.shape[0]:
+            raise RuntimeError("expression_key and spot_key must have one row per training spot")
+        genes = expr_t.shape[1]
+        expr_out = torch.empty((q, genes), device=key.device, dtype=torch.float32)
+    check(_lib.lib().mcl_knn_combine(
+        key.data_ptr(), key.stride(0), ops._p(expr_t), expr_t.stride(0) if expr_t is not None else 0,
+        qry.data_ptr(), qry.stride(0), idx.data_ptr(), q, k, key.shape[1], genes, COMBINE_MODES[method], emb.data_ptr(),
+        ops._p(expr_out), ops._stream()), "mcl_knn_combine")
+    return emb, expr_out
+
+
 def predict_expression(spot_key: ArrayLike, expression_key: ArrayLike, image_query: ArrayLike, top_k: int = 200,
                        ord: int = 2, method: str = "weighted") -> Dict[str, np.ndarray]:
     """The evaluation section of the reference's eval scripts for one fold (evel_her2st.py:158-187): retrieve the
     ``top_k`` training spots per image query and average them.  Returns numpy arrays ``indices`` (Q, top_k),
     ``matched_spot_embeddings_pred`` (Q, P) and ``matched_spot_expression_pred`` (Q, G), float64 like the
-    reference's ``np.zeros`` buffers."""
-    if method != "weighted":
-        raise ValueError("only the reference's active method 'weighted' is implemented")
+    reference's ``np.zeros`` buffers.  ``method``: ``"weighted"`` is mclSTExp's inverse-distance^2 weighting; ``"simple"``,
+    ``"average"`` and ``"weighted_average"`` are BLEEP's (``combine_device``; ``ord`` is ignored, ``"simple"`` uses the first
+    of the ``top_k`` matches)."""
+    if method != "weighted" and method not in COMBINE_MODES:
+        raise ValueError(f"method must be 'weighted' or one of {sorted(COMBINE_MODES)}, got {method!r}")
     key = to_device(spot_key, "spot_key")
     qry = to_device(image_query, "image_query")
     _, idx = find_matches_device(key, qry, top_k)
-    emb, expr = weighted_average_device(key, expression_key, qry, idx, ord)
+    if method == "weighted":
+        emb, expr = weighted_average_device(key, expression_key, qry, idx, ord)
+    else:
+        emb, expr = combine_device(key, expression_key, qry, idx, method)
     return {"indices": idx.cpu().numpy(),
             "matched_spot_embeddings_pred": emb.cpu().numpy().astype(np.float64),
             "matched_spot_expression_pred": expr.cpu().numpy().astype(np.float64)}
