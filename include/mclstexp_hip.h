@@ -978,6 +978,62 @@ int mcl_expression_matrices(const void* const* slides, const int64_t* ld, const 
                             const int64_t* row_offsets, int32_t dtype, const int32_t* sel, int32_t S, int32_t K,
                             int32_t max_rows, float rescale, float* out, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- Harmony batch correction (ABI 13, entry points added;
+ * csrc/harmony.hip).  BLEEP's preprocess.ipynb, last cell: harmonypy.run_harmony on the slides' concatenated hvg_matrix.npy.
+ * The arithmetic is stated in DESIGN 6.9.  Common contract: cells are rows; Z, Zc, Z_corr (N, d), R, S, D (N, K),
+ * Y (K, d), E, O (K, B) are dense row-major fp64 device matrices; batch[n] in [0, B) and order[] (a permutation of
+ * 0 .. N - 1) are device int32 the caller has checked (an entry out of range is read as the nearest valid one); theta,
+ * lamb, Pr are B device doubles.  K <= 128, B <= 31, N * K < 2^31 (and d <= 2^22 in mcl_harmony_ridge and
+ * mcl_harmony_apply): MCL_EUNSUPPORTED beyond.  No floating-point atomics,
+ * no kernel waits on another workgroup, every summation order is a function of the shapes alone: bit-identical run to run.
+ *
+ * mcl_harmony_workspace_doubles: the doubles `work` must hold for (N, K, d, B) in every entry point below that takes it.
+ * mcl_harmony_normalize: z (N, d), leading dimension ld, dtype 0 = float32 / 1 = float64.  zc = the rows of z divided by
+ *   their own maximum (divide_by_max != 0; a zero maximum gives NaN, a negative one flips the sign, as harmonypy does) and
+ *   then by their L2 norm; a NaN anywhere in a row makes its maximum NaN (numpy's max), so the whole row becomes NaN.
+ *   z64 (may be NULL) = z converted to fp64.  zc may be z itself when z is dense fp64.
+ * mcl_harmony_centroids: out = A X reduced over the N cells on v_mfma_f64_16x16x4_f64, N cut into slices fixed by the
+ *   shapes and merged in slice order.  B == 0: out (K, d) = R^T X, normalize != 0 then L2-normalises its rows (step 2a).
+ *   B > 0: out (K, B + 1, d): row (k, 0) = sum_n R[n][k] X[n], row (k, b + 1) the same over the cells of batch b (the
+ *   correction's M_k), the operand formed on load.
+ * mcl_harmony_dist: D = 2 (1 - Zc Y^T) (raw != 0: the product itself), reduced over d in index order on the same MFMA.
+ * mcl_harmony_softmax: out[n][k] = exp(-D[n][k] / sigma - max_k(-D[n][k] / sigma)); normalize != 0: divided by its row sum.
+ * mcl_harmony_moments: E[k][b] = (sum_n R[n][k]) Pr[b], O[k][b] = sum_{n in b} R[n][k].
+ * mcl_harmony_update_block: step 2d for the blocks [block_lo, block_hi) of numpy.array_split(order, n_blocks), in order:
+ *   the block's sums of R leave E and O, R[n][k] = S[n][k] ((E[k][b] + 1) / (O[k][b] + 1))^theta[b] divided by the row's L1
+ *   norm, the new sums enter E and O.  Three launches per block; block sums by a fixed tree.
+ * mcl_harmony_objective: out3 = { sum R D, sigma sum R log R (a non-finite term counts 0),
+ *   sigma sum R[n][k] theta[b(n)] log((O[k][b(n)] + 1) / (E[k][b(n)] + 1)) }.
+ * mcl_harmony_ridge: M (K, B + 1, d) from mcl_harmony_centroids.  A_k = arrow(O[k]) + diag(0, lamb) is inverted by
+ *   Gauss-Jordan with partial pivoting; W (K, B + 1, d) = A_k^-1 M_k with row (k, 0) set to 0.
+ * mcl_harmony_apply: out[n] = Z[n] - sum_k R[n][k] W[k][batch[n] + 1]; out must not be Z.
+ * mcl_harmony_lloyd: the hard k-means that seeds Y when no centroids are given: Y = the rows seed_rows[K] of Zc, then iters
+ *   times: label = argmax_k Zc Y^T (ties: the lowest centre), Y[k] = the mean of its cells (an emptied centre keeps its
+ *   row); finally the rows of Y are L2-normalised.  labels (N) int32, products (N, K), sums (K, d): scratch / results.   */
+int64_t mcl_harmony_workspace_doubles(int32_t N, int32_t K, int32_t d, int32_t B);
+int mcl_harmony_normalize(const void* z, int64_t ld, int32_t dtype, int32_t N, int32_t d, int32_t divide_by_max,
+                          double* z64, double* zc, mcl_stream_t stream);
+int mcl_harmony_centroids(const double* R, const double* X, const int32_t* batch, int32_t N, int32_t K, int32_t d,
+                          int32_t B, int32_t normalize, double* work, double* out, mcl_stream_t stream);
+int mcl_harmony_dist(const double* Zc, const double* Y, int32_t N, int32_t K, int32_t d, int32_t raw, double* D,
+                     mcl_stream_t stream);
+int mcl_harmony_softmax(const double* D, int32_t N, int32_t K, double sigma, int32_t normalize, double* out,
+                        mcl_stream_t stream);
+int mcl_harmony_moments(const double* R, const int32_t* batch, int32_t N, int32_t K, int32_t B, const double* Pr, double* E,
+                        double* O, mcl_stream_t stream);
+int mcl_harmony_update_block(double* R, const double* S, const int32_t* batch, const int32_t* order, int32_t N, int32_t K,
+                             int32_t B, int32_t n_blocks, int32_t block_lo, int32_t block_hi, const double* theta,
+                             const double* Pr, double* E, double* O, mcl_stream_t stream);
+int mcl_harmony_objective(const double* R, const double* D, const int32_t* batch, const double* E, const double* O,
+                          const double* theta, int32_t N, int32_t K, int32_t B, double sigma, double* work, double* out3,
+                          mcl_stream_t stream);
+int mcl_harmony_ridge(const double* O, const double* M, const double* lamb, int32_t K, int32_t B, int32_t d, double* W,
+                      mcl_stream_t stream);
+int mcl_harmony_apply(const double* Z, const double* R, const double* W, const int32_t* batch, int32_t N, int32_t K,
+                      int32_t B, int32_t d, double* out, mcl_stream_t stream);
+int mcl_harmony_lloyd(const double* Zc, int32_t N, int32_t K, int32_t d, const int32_t* seed_rows, int32_t iters,
+                      int32_t* labels, double* products, double* sums, double* work, double* Y, mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -226,6 +226,17 @@ PROTOTYPES = {
     "mcl_hvg_stats": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_hvg_pool": [c_p, c_i, c_i, c_p, c_i, c_p, c_p, c_p],
     "mcl_expression_matrices": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_i, c_i, c_f, c_p, c_p],
+    "mcl_harmony_workspace_doubles": [c_i, c_i, c_i, c_i],
+    "mcl_harmony_normalize": [c_p, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "mcl_harmony_centroids": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "mcl_harmony_dist": [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
+    "mcl_harmony_softmax": [c_p, c_i, c_i, c_d, c_i, c_p, c_p],
+    "mcl_harmony_moments": [c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
+    "mcl_harmony_update_block": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "mcl_harmony_objective": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_d, c_p, c_p, c_p],
+    "mcl_harmony_ridge": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
+    "mcl_harmony_apply": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
+    "mcl_harmony_lloyd": [c_p, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32, "mcl_gemm_args_min_size": C.c_uint32, "mcl_dense_block_fwd_workspace_bytes": C.c_int64, "mcl_dense_block_bwd_workspace_bytes": C.c_int64, "mcl_bn_workspace_floats": C.c_int64,
              "mcl_infonce_fused_workspace_bytes": C.c_int64, "mcl_dense_conv1x1_workspace_floats": C.c_int64,
@@ -235,7 +246,7 @@ _RESTYPES = {"mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32, "
              "mcl_conv0_wrw_workspace_floats": C.c_int64, "mcl_infonce_fp8_workspace_bytes": C.c_int64,
              "mcl_gemm_bf16_workspace_floats": C.c_int64, "mcl_colred_workspace_floats": C.c_int64,
              "mcl_gemm_workspace_floats": C.c_int64, "mcl_rowred_workspace_floats": C.c_int64,
-             "mcl_proj_head_ws_floats": C.c_int64}
+             "mcl_proj_head_ws_floats": C.c_int64, "mcl_harmony_workspace_doubles": C.c_int64}
 
 
 def load(path: str = LIB_PATH) -> C.CDLL:
