@@ -1034,6 +1034,39 @@ int mcl_harmony_apply(const double* Z, const double* R, const double* W, const i
 int mcl_harmony_lloyd(const double* Zc, int32_t N, int32_t K, int32_t d, const int32_t* seed_rows, int32_t iters,
                       int32_t* labels, double* products, double* sums, double* work, double* Y, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- exact t-SNE in two dimensions (ABI 13, entry points added;
+ * csrc/tsne.hip).  sklearn.manifold.TSNE(method="exact"), degrees of freedom 1, for every segment (slide) of a row-stacked
+ * matrix; the arithmetic is stated in DESIGN 6.10.  Common contract: offsets (S + 1) and pair_offsets (S + 1, the running
+ * sum of n_s^2) are device int64 the caller has checked; rows = offsets[S], min_n / max_n the smallest / largest n_s and
+ * pairs = pair_offsets[S] are the caller's statement of them, by which the launches are sized (a segment that does not fit
+ * them is skipped).  P holds one dense (n_s, n_s) fp64 matrix per segment at pair_offsets[s]; Y, grad, update, gains are
+ * dense (rows, 2) fp64, 16-byte aligned.  seg_params (S, 5) device doubles: exaggeration, momentum, learning rate, active
+ * (0: the segment is skipped by mcl_tsne_gradient and mcl_tsne_update), reset (!= 0: update and gains are read as 0 and 1).
+ * 2 <= n_s <= 16384, pairs <= 2^31, S <= 65535, D <= 64: MCL_EUNSUPPORTED beyond.  fp64 throughout, no floating-point
+ * atomics, no kernel waits on another workgroup, every summation order is a function of n_s alone: a segment inside a
+ * batch is bit-identical to the same segment alone.
+ *
+ * mcl_tsne_workspace_doubles: the doubles `work` must hold for (rows, S) in the entry points below.
+ * mcl_tsne_affinities: x (rows, D), leading dimension ld, dtype 0 = float32 / 1 = float64.  d_ij = sum_k (x_ik - x_jk)^2
+ *   in index order without contraction (float32_distances != 0: rounded to float32 and back, sklearn's arithmetic), the
+ *   per-row precision search of sklearn's _binary_search_perplexity (perplexity < min_n), P = max((C + C^T) / sum, eps)
+ *   with a zero diagonal.  beta (rows): the precision each row's conditional distribution was made with.
+ * mcl_tsne_gradient: grad_i = 4 (sum_j p'_ij w_ij (y_i - y_j) - (sum_j w_ij^2 (y_i - y_j)) / sum Q), p' = exaggeration p,
+ *   w_ij = 1 / (1 + |y_i - y_j|^2), sum Q over i != j.  want_kl != 0: kl[s] = sum p' log(max(p', eps) sum Q / w).
+ * mcl_tsne_update: gain += 0.2 where update * grad < 0, else *= 0.8, floored at 0.01; update = momentum update -
+ *   learning rate gain grad; Y += update; grad_norm2[s] = the squared norm of gain * grad.                              */
+int64_t mcl_tsne_workspace_doubles(int32_t rows, int32_t S);
+int mcl_tsne_affinities(const void* x, int64_t ld, int32_t dtype, int32_t D, const int64_t* offsets,
+                        const int64_t* pair_offsets, int32_t S, int32_t rows, int32_t min_n, int32_t max_n, int64_t pairs,
+                        double perplexity, int32_t float32_distances, double* work, double* P, double* beta,
+                        mcl_stream_t stream);
+int mcl_tsne_gradient(const double* P, const int64_t* pair_offsets, const double* Y, const int64_t* offsets, int32_t S,
+                      int32_t rows, int32_t min_n, int32_t max_n, int64_t pairs, const double* seg_params, int32_t want_kl,
+                      double* work, double* grad, double* kl, mcl_stream_t stream);
+int mcl_tsne_update(const double* grad, const int64_t* offsets, int32_t S, int32_t rows, int32_t min_n, int32_t max_n,
+                    const double* seg_params, double* Y, double* update, double* gains, double* grad_norm2,
+                    mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -8,12 +8,13 @@ All slides of an evaluation run through ONE ``mcl_pca_gram`` / ``mcl_pca_project
 ``mcl_cluster_scores`` call each (csrc/cluster.hip: fp64, deterministic, a slide inside a batch is bit-identical to the same
 slide alone).  Host side on purpose: the label strings -> integer codes and the row mask (bookkeeping), and
 ``numpy.linalg.eigh`` of the one small symmetric Gram matrix per slide (a device eigensolver is out of scope).  t-SNE, which
-the reference computes and never reads, is not reproduced.  Seeding: the reference's k-means++ draws from NumPy's
+the reference computes and never reads, is opt-in (``tsne=True`` / ``--tsne OUT.npz``: ``mclstexp_amd.tsne`` embeds the PCA
+scores already at hand; the scores and clusters do not depend on it).  Seeding: the reference's k-means++ draws from NumPy's
 ``RandomState(0)``; that stream is NOT reproduced -- ``seed_rows`` replays given initial centres exactly, otherwise the
 kernel's own k-means++ (counter-based generator) is used, best of ``n_init`` restarts.  No CPU fallback: without a GPU /
 the HIP library these functions raise ``RuntimeError``.
 
-    python -m mclstexp_amd.cluster --pred P1.npy ... --labels L1.npy ... [--n_init N] [--json OUT]
+    python -m mclstexp_amd.cluster --pred P1.npy ... --labels L1.npy ... [--n_init N] [--json OUT] [--tsne OUT.npz]
 """
 from __future__ import annotations
 
@@ -267,12 +268,14 @@ def _take_rows(x: ArrayLike, idx: np.ndarray, dev: torch.device) -> ArrayLike:
 
 def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undetermined="undetermined",
                    n_comps: int = N_COMPS, seed_rows=None, n_init: int = 1, seed: int = 0, tol: float = 1e-4,
-                   max_iter: int = 300, segment_base: int = 0) -> Dict[str, object]:
+                   max_iter: int = 300, segment_base: int = 0, tsne: Union[bool, dict] = False) -> Dict[str, object]:
     """cluster() for every slide of an evaluation in ONE gram / ONE project / ONE kmeans / ONE scores call.
     ``preds[i]``: (spots_i, genes) predicted expression, ``labels[i]``: (spots_i,) annotations.  Returns ``slides``: per
     slide ``p`` (cluster index per kept spot, int32), ``ari``, ``nmi`` (rounded to 3 decimals as the reference does),
     ``ari_raw``, ``nmi_raw``, ``k``, ``inertia``, ``n_iter``, ``restart``; and ``ari``, ``nmi``: the means over slides of
-    the rounded values."""
+    the rounded values.  ``tsne`` (True, or a dict of ``mclstexp_amd.tsne.tsne`` arguments): every slide also gets ``tsne``,
+    the (kept spots, 2) exact t-SNE embedding of its PCA scores (the reference's ``sc.tl.tsne``), as a numpy array;
+    everything else is what ``tsne=False`` gives."""
     if len(preds) != len(labels) or not len(preds):
         raise ValueError(f"need one label vector per prediction and >= 1 slide; got {len(preds)} and {len(labels)}")
     enc = []
@@ -296,18 +299,25 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
     slides = [{"p": p_all[off[i]:off[i + 1]].copy(), "ari": round(float(ari[i]), 3), "nmi": round(float(nmi[i]), 3),
                "ari_raw": float(ari[i]), "nmi_raw": float(nmi[i]), "k": int(ks[i]), "inertia": float(inertia[i]),
                "n_iter": int(n_iter[i]), "restart": int(restart[i])} for i in range(len(preds))]
+    if tsne is not False and tsne is not None:
+        from . import tsne as tsne_module             # tsne imports this module
+        emb = tsne_module.tsne(z, off, **(tsne if isinstance(tsne, dict) else {}))["embedding"].cpu().numpy()
+        for i, s in enumerate(slides):
+            s["tsne"] = emb[off[i]:off[i + 1]].copy()
     return {"slides": slides, "ari": float(np.mean([s["ari"] for s in slides])),
             "nmi": float(np.mean([s["nmi"] for s in slides]))}
 
 
 def cluster(pred: ArrayLike, label: Sequence, undetermined="undetermined", n_comps: int = N_COMPS, seed_rows=None,
-            n_init: int = 1, seed: int = 0) -> Tuple[np.ndarray, float, float]:
+            n_init: int = 1, seed: int = 0, tsne: Union[bool, dict] = False) -> tuple:
     """The reference's ``cluster(adata, label)`` -> ``(p, ari, nmi)``: ``p`` the cluster index of every kept spot,
     ``ari`` / ``nmi`` rounded to 3 decimals.  ``seed_rows`` (n_restarts, k) or (k,): initial centres as rows of the kept
-    spots."""
+    spots.  ``tsne`` (see ``cluster_slides``): ``(p, ari, nmi, embedding)``."""
     if seed_rows is not None:
         seed_rows = [np.asarray(seed_rows)]
-    s = cluster_slides([pred], [label], undetermined, n_comps, seed_rows, n_init, seed)["slides"][0]
+    s = cluster_slides([pred], [label], undetermined, n_comps, seed_rows, n_init, seed, tsne=tsne)["slides"][0]
+    if "tsne" in s:
+        return s["p"], s["ari"], s["nmi"], s["tsne"]
     return s["p"], s["ari"], s["nmi"]
 
 
@@ -323,6 +333,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--n_init", type=int, default=1, help="k-means restarts, the best inertia wins")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--json", default=None, help="also write per-slide and mean scores to this file")
+    p.add_argument("--tsne", default=None, metavar="OUT.npz",
+                   help="also embed every slide's PCA scores by exact t-SNE and write slide_<i> arrays (kept spots, 2)")
     a = p.parse_args(argv)
     if len(a.pred) != len(a.labels):
         p.error(f"{len(a.pred)} --pred files but {len(a.labels)} --labels files")
@@ -340,8 +352,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = parse_args(argv)
     preds = [np.load(f) for f in a.pred]
     labels = [np.load(f, allow_pickle=False) for f in a.labels]
-    res = cluster_slides(preds, labels, a.undetermined, a.n_comps, None, a.n_init, a.seed)
+    res = cluster_slides(preds, labels, a.undetermined, a.n_comps, None, a.n_init, a.seed, tsne=a.tsne is not None)
     print(format_report(res))
+    if a.tsne:
+        np.savez(a.tsne, **{f"slide_{i}": s.pop("tsne") for i, s in enumerate(res["slides"])})
     if a.json:
         doc = {"ari": res["ari"], "nmi": res["nmi"], "n_comps": a.n_comps, "n_init": a.n_init, "seed": a.seed,
                "slides": [{k: (v.tolist() if isinstance(v, np.ndarray) else v) for k, v in s.items()}
