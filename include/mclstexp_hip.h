@@ -1067,6 +1067,41 @@ int mcl_tsne_update(const double* grad, const int64_t* offsets, int32_t S, int32
                     const double* seg_params, double* Y, double* update, double* gains, double* grad_norm2,
                     mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- the spot neighbourhood graph (ABI 13, entry points added;
+ * csrc/neighbors.hip).  scanpy's sc.pp.neighbors with umap-learn's weights, exact at every size, for every segment (slide)
+ * of a row-stacked matrix; the arithmetic is stated in DESIGN 6.11.  Common contract: offsets (S + 1) is device int64 the
+ * caller has checked; rows = offsets[S], min_n / max_n the smallest / largest n_s are the caller's statement of them, by
+ * which the launches are sized (a segment that does not fit them is skipped).  k = n_neighbors counts the row itself.
+ * 2 <= k <= 256, k <= n_s, 2 <= n_s <= 16384, S <= 65535, D <= 64: MCL_EUNSUPPORTED beyond the upper limits, MCL_EINVAL
+ * below the lower ones.  fp64 throughout, no floating-point atomics, no result depends on the order workgroups arrive in:
+ * a segment inside a batch is bit-identical to the same segment alone.
+ *
+ * mcl_knn_workspace_bytes: the bytes `work` must hold for (rows, k) in mcl_knn_smooth and mcl_knn_connectivities (8-byte
+ *   aligned; the two phases of mcl_knn_connectivities share its contents).
+ * mcl_knn_exact: x (rows, D), leading dimension ld, dtype 0 = float32 / 1 = float64.  d2_ij = sum_c (x_ic - x_jc)^2 in index
+ *   order without contraction.  knn_indices (rows, k) int32, segment-local: position 0 is the row itself at distance 0,
+ *   positions 1 .. k-1 the other rows in ascending (d2, j); knn_distances (rows, k) = sqrt(d2).
+ * mcl_knn_smooth: umap-learn's smooth_knn_dist(n_iter 64, local_connectivity 1, bandwidth 1) per row: rho (rows) the
+ *   smallest positive distance or 0, sigma (rows) the bisection's last mid after the floors 1e-3 x the row's / the
+ *   segment's mean distance.
+ * mcl_knn_connectivities: the directed weights (0 for the row itself, 1 where d - rho <= 0 or sigma == 0, else
+ *   exp(-(d - rho) / sigma)), united as w = mix (a + b - a b) + (1 - mix) a b, as one CSR per segment without the diagonal
+ *   and without zeros, columns ascending.  phase 0: fills work, writes indptr (rows + S int64: segment s holds n_s + 1
+ *   entries from offsets[s] + s, starting at 0) and nnz (S int64; -1 for a skipped segment).  phase 1, after phase 0 on
+ *   the same arguments and work: nnz_offsets (S + 1 device int64, the running sum of nnz) places segment s in indices
+ *   (int32) and data (fp64), each of nnz_total entries; nothing is written beyond them.                                  */
+int64_t mcl_knn_workspace_bytes(int32_t rows, int32_t k);
+int mcl_knn_exact(const void* x, int64_t ld, int32_t dtype, int32_t D, const int64_t* offsets, int32_t S, int32_t rows,
+                  int32_t min_n, int32_t max_n, int32_t k, int32_t* knn_indices, double* knn_distances,
+                  mcl_stream_t stream);
+int mcl_knn_smooth(const double* knn_distances, const int64_t* offsets, int32_t S, int32_t rows, int32_t min_n,
+                   int32_t max_n, int32_t k, void* work, double* rho, double* sigma, mcl_stream_t stream);
+int mcl_knn_connectivities(const int32_t* knn_indices, const double* knn_distances, const double* rho, const double* sigma,
+                           const int64_t* offsets, int32_t S, int32_t rows, int32_t min_n, int32_t max_n, int32_t k,
+                           double set_op_mix_ratio, int32_t phase, void* work, int64_t* indptr, int64_t* nnz,
+                           const int64_t* nnz_offsets, int64_t nnz_total, int32_t* indices, double* data,
+                           mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -73,6 +73,21 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// csrc/tsne.hip, csrc/neighbors.hip: d_ij = sum_k (x_ik - x_jk)^2 in index order, products and sums rounded separately (no
+// contraction: the value is the one numpy's elementwise arithmetic gives, so two kernels -- and the float32 rounding of
+// t-SNE's float32_distances -- agree with the restatements bit for bit)
+template <typename T>
+__device__ __forceinline__ double ts_sqdist(const double* xi, const T* xj, int D) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+  for (int k = 0; k < D; ++k) {
+    const double diff = xi[k] - (double)xj[k];
+    const double sq = diff * diff;
+    acc = acc + sq;
+  }
+  return acc;
+}
+
 // exact-erf GELU (nn.GELU() default) and its derivative
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {

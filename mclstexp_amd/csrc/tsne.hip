@@ -59,20 +59,7 @@ __device__ __forceinline__ bool ts_segment(const long long* off, const long long
 }
 
 // ------------------------------------------------------------------------------------------------------- affinities
-// d_ij = sum_k (x_ik - x_jk)^2 in index order, products and sums rounded separately (no contraction: the value is the one
-// numpy's elementwise arithmetic gives, so the float32 rounding of float32_distances falls the same way everywhere)
-template <typename T>
-__device__ __forceinline__ double ts_sqdist(const double* xi, const T* xj, int D) {
-#pragma clang fp contract(off)
-  double acc = 0.0;
-  for (int k = 0; k < D; ++k) {
-    const double diff = xi[k] - (double)xj[k];
-    const double sq = diff * diff;
-    acc = acc + sq;
-  }
-  return acc;
-}
-
+// d_ij: ts_sqdist (common.h), shared with neighbors.hip
 template <typename T>
 __global__ __launch_bounds__(TS_THREADS) void ts_affinity_kernel(const T* __restrict__ x, long long ld, int D,
                                                                  const long long* __restrict__ off,
