@@ -1102,6 +1102,42 @@ int mcl_knn_connectivities(const int32_t* knn_indices, const double* knn_distanc
                            const int64_t* nnz_offsets, int64_t nnz_total, int32_t* indices, double* data,
                            mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- the UMAP layout of that graph (ABI 13, entry points added;
+ * csrc/umap.hip).  scanpy's sc.tl.umap on the connectivities CSR of mcl_knn_connectivities for every segment (slide); the
+ * arithmetic is stated in DESIGN 6.12: one Jacobi step per epoch (every gradient of epoch n at the positions at its start),
+ * negative samples a pure function of (seed, epoch, vertex, entry rank, sample number).  Common contract: offsets (S + 1),
+ * nnz_offsets (S + 1) device int64 and n_epochs (S) device int32 the caller has checked; rows, min_n, max_n, nnz_total =
+ * nnz_offsets[S], max_nnz (the most entries of one segment) and max_epochs (the largest n_epochs) are the caller's statement
+ * of them, by which the launches are sized (a segment that does not fit them is skipped; a column outside its segment is
+ * ignored; a weight that is not positive and finite is never sampled).  indptr / indices / data as mcl_knn_connectivities
+ * leaves them: exactly symmetric, no diagonal, columns ascending.  Positions are dense (rows, 2) fp64, 16-byte aligned.
+ * 2 <= n_s <= 16384, S <= 65535, 1 <= n_epochs <= 5000, 0 <= negative_sample_rate <= 64, a, b, gamma, alpha finite and
+ * a, b > 0: MCL_EUNSUPPORTED otherwise.  fp64 throughout, no floating-point atomics (integer atomics count the samples), no
+ * workgroup waits on another: a segment inside a batch is bit-identical to the same segment alone.
+ *
+ * mcl_umap_workspace_bytes: the bytes `work` must hold (8-byte aligned); it carries the schedule from mcl_umap_prepare
+ *   through every mcl_umap_epochs call of one layout.
+ * mcl_umap_prepare: per segment wmax = its largest weight; per stored entry live = w >= wmax / n_epochs, eps = wmax / w,
+ *   epn = eps / negative_sample_rate, next = eps, nneg = epn, each a single IEEE operation.  Zeroes counters (S, 2).
+ * mcl_umap_init: mode 0: Y = the first two columns of x (rows, D >= 2; leading dimension ld, dtype 0 = float32 / 1 =
+ *   float64) times 10 / (the segment's largest absolute value in them); mode 1: y_ic = 20 ((h >> 11) 2^-53) - 10 with
+ *   h = mix(mix(mix(seed ^ ~0) ^ i) ^ c), mix the splitmix64 step (x is not read).
+ * mcl_umap_epochs: epochs first .. first + count - 1, one launch each, enqueued back to back.  Epoch n reads Y0 when n is
+ *   even and Y1 when it is odd and writes the other; a segment with n >= n_epochs[s] copies its positions across, so after
+ *   epoch n every segment's current positions are in the buffer of parity n + 1.  The same work, counters and arguments as
+ *   in mcl_umap_prepare; every epoch exactly once, in order.  counters[s] = (attractions taken, negative samples drawn). */
+int64_t mcl_umap_workspace_bytes(int64_t nnz_total, int32_t S);
+int mcl_umap_prepare(const double* data, const int64_t* nnz_offsets, const int32_t* n_epochs, int32_t S, int64_t nnz_total,
+                     int64_t max_nnz, int32_t max_epochs, int32_t negative_sample_rate, void* work, int64_t* counters,
+                     mcl_stream_t stream);
+int mcl_umap_init(int32_t mode, const void* x, int64_t ld, int32_t dtype, int32_t D, const int64_t* offsets, int32_t S,
+                  int32_t rows, int32_t min_n, int32_t max_n, uint64_t seed, double* Y, mcl_stream_t stream);
+int mcl_umap_epochs(int32_t first, int32_t count, const int64_t* indptr, const int32_t* indices, const int64_t* offsets,
+                    const int64_t* nnz_offsets, const int32_t* n_epochs, int32_t S, int32_t rows, int32_t min_n,
+                    int32_t max_n, int64_t nnz_total, int32_t max_epochs, double a, double b, double gamma, double alpha,
+                    int32_t negative_sample_rate, uint64_t seed, void* work, double* Y0, double* Y1, int64_t* counters,
+                    mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

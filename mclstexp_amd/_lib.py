@@ -246,6 +246,11 @@ PROTOTYPES = {
     "mcl_knn_smooth": [c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p],
     "mcl_knn_connectivities": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_d, c_i, c_p, c_p, c_p, c_p, c_l, c_p, c_p,
                                c_p],
+    "mcl_umap_workspace_bytes": [c_l, c_i],
+    "mcl_umap_prepare": [c_p, c_p, c_p, c_i, c_l, c_l, c_i, c_i, c_p, c_p, c_p],
+    "mcl_umap_init": [c_i, c_p, c_l, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_uint64, c_p, c_p],
+    "mcl_umap_epochs": [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_i, c_d, c_d, c_d, c_d, c_i, C.c_uint64,
+                        c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32, "mcl_gemm_args_min_size": C.c_uint32, "mcl_dense_block_fwd_workspace_bytes": C.c_int64, "mcl_dense_block_bwd_workspace_bytes": C.c_int64, "mcl_bn_workspace_floats": C.c_int64,
              "mcl_infonce_fused_workspace_bytes": C.c_int64, "mcl_dense_conv1x1_workspace_floats": C.c_int64,
@@ -256,7 +261,8 @@ _RESTYPES = {"mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32, "
              "mcl_gemm_bf16_workspace_floats": C.c_int64, "mcl_colred_workspace_floats": C.c_int64,
              "mcl_gemm_workspace_floats": C.c_int64, "mcl_rowred_workspace_floats": C.c_int64,
              "mcl_proj_head_ws_floats": C.c_int64, "mcl_harmony_workspace_doubles": C.c_int64,
-             "mcl_tsne_workspace_doubles": C.c_int64, "mcl_knn_workspace_bytes": C.c_int64}
+             "mcl_tsne_workspace_doubles": C.c_int64, "mcl_knn_workspace_bytes": C.c_int64,
+             "mcl_umap_workspace_bytes": C.c_int64}
 
 
 def load(path: str = LIB_PATH) -> C.CDLL:
