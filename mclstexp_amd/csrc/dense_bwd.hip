@@ -7,16 +7,18 @@
 //
 // The stock sequence materialises da (S x C_in), re-reads it together with x for the two reductions and reads it a
 // third time with x and the gradient buffer for dx: 7 passes over the O(L^2) S x C_in data of a dense block.  Here
-// da never exists: a "reduce" launch and a "dx" launch both recompute their 128 x 128 tile of dz W1 on the matrix
-// cores (K = 128: 2 x 32 MFMAs per wave, ~1 % of the step's FLOPs) and touch HBM only for x (once each) and the
+// da never exists: a "reduce" launch and a "dx" launch both recompute their 64 x 128 tile of dz W1 on the matrix
+// cores (K = 128: 16 MFMAs per wave and tile, ~1 % of the step's FLOPs) and touch HBM only for x (once each) and the
 // gradient buffer (read-modify-write): 4 passes, and no MIOpen backward-data call with its zero-fill helper.
 //
-// Tile = 128 pixels x 128 input channels, 4 waves (2 x 2, each 64 x 64 as 2 x 2 v_mfma_f32_32x32x16_bf16), two
-// workgroups per CU.  dz tile and the W1 column block are staged once (K = 128 needs no loop): dz rows XOR-swizzled
-// for ds_read_b128 fragments, W1 rows read with ds_read_b64_tr_b16 (k-strided operand).  After the MFMAs the same LDS
-// is reused to stage the x tile and (dx launch) the gradient-buffer tile with full 16-byte row chunks, because the
-// accumulator layout (lane = channel) would otherwise touch HBM in 64-byte fragments; the per-channel BatchNorm
-// constants live in registers (a lane keeps its channel for the whole tile).
+// Tile = 64 pixels x 128 input channels (TMv; the template allows 128, every host launches 64: three workgroups per CU
+// for the reduce and dx launches, two for the single-pass and the paired dx), 4 waves (2 x 2, each 32 x 64 as 1 x 2
+// v_mfma_f32_32x32x16_bf16).  The W1 column block is staged once per workgroup and the dz tile once per row tile (K = 128
+// needs no loop): dz rows XOR-swizzled for ds_read_b128 fragments, W1 rows read with ds_read_b64_tr_b16 (k-strided operand).
+// After the MFMAs the same LDS is reused to stage the x tile and (dx launches) the bf16 deltas with full 16-byte row chunks,
+// because the accumulator layout (lane = channel) would otherwise touch HBM in 64-byte fragments; the per-channel BatchNorm
+// constants live in registers (a lane keeps its channel for the whole tile).  How the global loads are scheduled: at
+// bn1_bwd_kernel below.
 #include "common.h"
 #include <stdlib.h>
 
@@ -24,15 +26,23 @@ namespace {
 
 constexpr int TN = 128, TK = 128;   // input channels, bottleneck channels per tile (pixels per tile: template TMv)
 
+// v where ``keep``, else zeros: a bounds mask applied to a loaded chunk (a select per word; the load itself is unconditional)
+__device__ __forceinline__ uint4 keep4(bool keep, const uint4 v) {
+  return make_uint4(keep ? v.x : 0u, keep ? v.y : 0u, keep ? v.z : 0u, keep ? v.w : 0u);
+}
+
 // MODE 0: reduce (partials of sum g, sum g*xhat)      MODE 1: dx accumulate
 // MODE 2: ONE pass -- gbuf += gamma*rstd*g (the data-dependent term of dx) AND the partials of the two sums.  The layer's own
 // two mean terms, per-channel constants times (1, xhat), are not known yet: they are applied ONE LAYER LATE, by the next
 // layer's pass over the same channels (``coef`` = the previous pass's finalized terms, NULL for the first layer of a block's
 // backward), and by bn1_fix_kernel for the 32 channels the next layer does not read
 // A workgroup keeps ONE column tile (its W1 block and per-channel constants are loaded once) and walks row tiles.
-// All global loads of a row tile (dz, x and -- dx launch -- the gradient-buffer chunks) are issued together at the
-// top, so the x / gradient latency hides under the dz staging and the MFMAs; LDS holds W1 (32 KB) + one 32 KB tile
-// that is first dz, then x, then (dx launch) the bf16 deltas: 64 KB, two workgroups per CU.
+// The global loads of a row tile (dz, x and -- dx launches -- the gradient-buffer chunks) stage through three register
+// sets.  The first tile's go out in the prologue together with the W1 block and the per-channel constants, behind one
+// wait; after that each set is refilled for the workgroup's NEXT row tile as soon as the current tile's copy has left it
+// (dz and x: written to LDS; the gradient chunks: added and stored), so a workgroup has loads in flight while it
+// multiplies, runs the epilogue and stores.  LDS holds W1 (32 KB) + one tile (TMv x 256 B) that is
+// first dz, then x, then (dx launches) the bf16 deltas.
 template <int MODE, int TMv>
 __global__ __launch_bounds__(256, (TMv == 64 && MODE != 2 ? 3 : 2)) void bn1_bwd_kernel(const bf16_t* __restrict__ dz, const bf16_t* __restrict__ W1,
                                                          int K /* channels of this launch */, int ldw /* row length of W1 (>= K: a channel window) */,
@@ -56,65 +66,97 @@ __global__ __launch_bounds__(256, (TMv == 64 && MODE != 2 ? 3 : 2)) void bn1_bwd
 
   const int cc = tid & 15, rr = tid >> 4;
   const bool cok = n0 + cc * 8 < K;
-  // ---- the first row tile's global loads go out BEFORE the once-per-workgroup staging below (otherwise they would wait
-  // behind its memory round trip: on the small maps a workgroup multiplies one to four tiles)
+  if ((int)blockIdx.x >= nrt) return;   // never with the hosts' grids (gx <= nrt): below, the first tile is unconditional
+  // Every global load below is unconditional: the row is clamped to S - 1, a chunk past the launch's channels to the first
+  // chunk of this column tile (n0 < K always) and a channel to K - 1, and ok / cok / cvalid are applied where the value is
+  // used, with selects (never a product: columns a launch may not use can hold NaN).  No load sits in a bounds branch, so
+  // the compiler keeps them back to back and each wait falls at its first consumer.
   constexpr int NL = TMv / 16, RI = TMv / 64;   // 16-byte chunks per thread and tile; 32-row blocks per wave
+  // MODE 0 (the reduce launch of the two-pass form) keeps all loads of a row tile at the top of its trip: it sits at the
+  // register limit of three workgroups per CU, and a set held across the tile would spill
+  constexpr bool PF = MODE != 0;
+  const int colc = cok ? n0 + cc * 8 : n0;
   uint4 dzr[NL], xr[NL], gr[NL];
-  auto issue_loads = [&](int rt) {
-    const long long row0 = (long long)rt * TMv;
+  // row of chunk i: of the row tile that starts at ``base``, or -- ``spread`` off, the dummy refill behind the last tile -- ``base``
+  auto rowc = [&](long long base, bool spread, int i) { return spread ? min(base + rr + 16 * i, S - 1) : base; };
+  auto load_dz = [&](long long base, bool spread) {
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const long long rg = row0 + rr + 16 * i;
-      const bool ok = rg < S;
-      dzr[i] = ok ? *reinterpret_cast<const uint4*>(dz + rg * TK + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      xr[i] = (ok && cok) ? *reinterpret_cast<const uint4*>(x + rg * ldx + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      if (MODE >= 1)
-        gr[i] = (ok && cok) ? *reinterpret_cast<const uint4*>(gbuf + rg * ldg + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
+    for (int i = 0; i < NL; ++i) dzr[i] = *reinterpret_cast<const uint4*>(dz + rowc(base, spread, i) * TK + cc * 8);
   };
-  if ((int)blockIdx.x < nrt) issue_loads(blockIdx.x);
-  // ---- once per workgroup: W1[:, n0:n0+128] and the per-channel constants of this lane's two channels
+  auto load_x = [&](long long base, bool spread) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) xr[i] = *reinterpret_cast<const uint4*>(x + rowc(base, spread, i) * ldx + colc);
+  };
+  auto load_g = [&](long long base, bool spread) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) gr[i] = *reinterpret_cast<const uint4*>(gbuf + rowc(base, spread, i) * ldg + colc);
+  };
+  // ---- prologue, ONE dependent round trip: the per-channel constants of this lane's two channels go out first (they
+  // return first, so their use never waits on anything issued behind them), then the first row tile's dz, the W1 column
+  // block and the first tile's x, all before the first wait (the W1 staging's); the x chunks stay in flight across that
+  // staging.  The tile's gradient-buffer chunks, written here as well, the compiler issues behind the staging's waits:
+  // they are first needed at the read-modify-write.
+  const bool hc = MODE >= 1 && coef != nullptr;
+  float mu[2], rs[2], gm[2], bt[2], c1[2], c2[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = min(n0 + wn * 64 + j * 32 + l31, K - 1);
+    mu[j] = mean[c];
+    rs[j] = rstd[c];
+    gm[j] = gamma[c];
+    bt[j] = beta[c];
+    if (MODE >= 1) {
+      const float* cp = hc ? coef + 2 * c : mean + c;   // no previous pass: a valid address, the value is not used
+      c1[j] = cp[0];
+      c2[j] = cp[hc ? 1 : 0];
+    }
+  }
+  load_dz((long long)blockIdx.x * TMv, true);
   {
     uint4 wv[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int k = rr + 16 * i;
-      wv[i] = cok ? *reinterpret_cast<const uint4*>(W1 + (long long)k * ldw + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
+    for (int i = 0; i < 8; ++i) wv[i] = *reinterpret_cast<const uint4*>(W1 + (long long)(rr + 16 * i) * ldw + colc);
+    load_x((long long)blockIdx.x * TMv, true);
+    if (MODE >= 1) load_g((long long)blockIdx.x * TMv, true);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int k = rr + 16 * i;
       // swizzle for the transposing read: 4 consecutive k rows (k & 3) must land in 4 different 64-byte bank
       // windows -> XOR the chunk's bits 2-3 with (k & 3); bits 0-1 with ((k >> 2) & 3)
       const int f = ((k & 3) << 2) | ((k >> 2) & 3);
-      *reinterpret_cast<uint4*>(wt + k * 256 + ((cc ^ f) << 4)) = wv[i];
+      *reinterpret_cast<uint4*>(wt + k * 256 + ((cc ^ f) << 4)) = keep4(cok, wv[i]);
     }
   }
-  float mu[2], rs[2], sc[2], sh[2], c1[2], c2[2];
+  float sc[2], sh[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int c = n0 + wn * 64 + j * 32 + l31;
-    const bool cvalid = c < K;
-    mu[j] = cvalid ? mean[c] : 0.0f;
-    rs[j] = cvalid ? rstd[c] : 0.0f;
-    sc[j] = cvalid ? gamma[c] * rs[j] : 0.0f;
-    sh[j] = cvalid ? fmaf(-mu[j], sc[j], beta[c]) : 0.0f;
-    c1[j] = (MODE >= 1 && coef != nullptr && cvalid) ? coef[2 * c] : 0.0f;
-    c2[j] = (MODE >= 1 && coef != nullptr && cvalid) ? coef[2 * c + 1] : 0.0f;
+    const bool cvalid = n0 + wn * 64 + j * 32 + l31 < K;
+    mu[j] = cvalid ? mu[j] : 0.0f;
+    rs[j] = cvalid ? rs[j] : 0.0f;
+    sc[j] = cvalid ? gm[j] * rs[j] : 0.0f;
+    sh[j] = cvalid ? fmaf(-mu[j], sc[j], bt[j]) : 0.0f;
+    c1[j] = (hc && cvalid) ? c1[j] : 0.0f;
+    c2[j] = (hc && cvalid) ? c2[j] : 0.0f;
   }
   const int q = (lane & 15) >> 2, jj = lane & 3;
   const int g2 = 2 * ((lane >> 4) & 1) + (jj >> 1);
 
   for (int rt = blockIdx.x; rt < nrt; rt += gridDim.x) {
     const long long row0 = (long long)rt * TMv;
-    // ---- all global loads of this row tile, issued together (the first tile's are in flight already)
-    if (rt != (int)blockIdx.x) issue_loads(rt);
+    // Each register set is refilled for the workgroup's next row tile, rt + gridDim.x, as soon as this tile's copy has left
+    // it, so those loads fly under the MFMAs, the epilogue and the read-modify-write.  Behind the last tile the refill is a
+    // dummy (every lane reads the tile's own first row, never used): a branch round the loads would make the compiler size
+    // each counted wait for the path that skipped the later ones, which drains them.
+    const bool more = rt + (int)gridDim.x < nrt;
+    const long long nbase = more ? row0 + (long long)gridDim.x * TMv : row0;
+    if (!PF && rt != (int)blockIdx.x) { load_dz(row0, true); load_x(row0, true); if (MODE >= 1) load_g(row0, true); }
     __syncthreads();   // the previous row tile is done with the shared tile
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int r = rr + 16 * i;
-      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = dzr[i];
+      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = keep4(row0 + r < S, dzr[i]);
     }
+    if (PF) load_dz(nbase, more);
     __syncthreads();
 
     // ---- da tile = dz_tile (128 x 128k) . W1_tile (128k x 128n): wave (wm, wn) owns rows wm*64.., channels wn*64..
@@ -153,7 +195,9 @@ __global__ __launch_bounds__(256, (TMv == 64 && MODE != 2 ? 3 : 2)) void bn1_bwd
     }
     __syncthreads();   // dz tile dead: the same LDS now takes the x tile (plain 256-byte rows)
 #pragma unroll
-    for (int i = 0; i < NL; ++i) *reinterpret_cast<uint4*>(xt + (rr + 16 * i) * TN + cc * 8) = xr[i];
+    for (int i = 0; i < NL; ++i)
+      *reinterpret_cast<uint4*>(xt + (rr + 16 * i) * TN + cc * 8) = keep4(cok && row0 + rr + 16 * i < S, xr[i]);
+    if (PF) load_x(nbase, more);
     __syncthreads();
 
     // ---- epilogue: acc[i][j][r] is da at row wm*64 + i*32 + (r&3) + 8*(r>>2) + 4*h, channel wn*64 + j*32 + l31
@@ -223,6 +267,9 @@ __global__ __launch_bounds__(256, (TMv == 64 && MODE != 2 ? 3 : 2)) void bn1_bwd
           }
         }
       }
+      // the next tile's chunks of the gradient buffer (behind the last tile: this tile's first row again): like the rows
+      // just written, read and written by this workgroup alone in this launch
+      if (PF) load_g(nbase, more);
     }
   }
 }
@@ -253,49 +300,81 @@ __global__ __launch_bounds__(256, 2) void bn1_dx_pair_kernel(const bf16_t* __res
   const int cc = tid & 15, rr = tid >> 4;
   const bool cok = n0 + cc * 8 < K;
   constexpr int NL = TMv / 16;
+  if ((int)blockIdx.x >= nrt) return;   // never with the host's grid (gx <= nrt): below, the first tile is unconditional
+  // unconditional, clamped loads with the bounds applied at the use, as in bn1_bwd_kernel
+  const int colc = cok ? n0 + cc * 8 : n0;
   uint4 dar[NL], dbr[NL], xr[NL], gr[NL];
-  auto issue_loads = [&](int rt) {
-    const long long row0 = (long long)rt * TMv;
+  // row of chunk i: of the row tile that starts at ``base``, or -- ``spread`` off, the dummy refill behind the last tile -- ``base``
+  auto rowc = [&](long long base, bool spread, int i) { return spread ? min(base + rr + 16 * i, S - 1) : base; };
+  auto load_dzA = [&](long long base, bool spread) {
 #pragma unroll
-    for (int i = 0; i < NL; ++i) {
-      const long long rg = row0 + rr + 16 * i;
-      const bool ok = rg < S;
-      dar[i] = ok ? *reinterpret_cast<const uint4*>(dzA + rg * TK + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      dbr[i] = ok ? *reinterpret_cast<const uint4*>(dzB + rg * TK + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      xr[i] = (ok && cok) ? *reinterpret_cast<const uint4*>(x + rg * ldx + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      gr[i] = (ok && cok) ? *reinterpret_cast<const uint4*>(gbuf + rg * ldg + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-    }
+    for (int i = 0; i < NL; ++i) dar[i] = *reinterpret_cast<const uint4*>(dzA + rowc(base, spread, i) * TK + cc * 8);
   };
-  if ((int)blockIdx.x < nrt) issue_loads(blockIdx.x);
+  auto load_dzB = [&](long long base, bool spread) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) dbr[i] = *reinterpret_cast<const uint4*>(dzB + rowc(base, spread, i) * TK + cc * 8);
+  };
+  auto load_x = [&](long long base, bool spread) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) xr[i] = *reinterpret_cast<const uint4*>(x + rowc(base, spread, i) * ldx + colc);
+  };
+  auto load_g = [&](long long base, bool spread) {
+#pragma unroll
+    for (int i = 0; i < NL; ++i) gr[i] = *reinterpret_cast<const uint4*>(gbuf + rowc(base, spread, i) * ldg + colc);
+  };
+  // ---- prologue, ONE dependent round trip: the constants first, then both weight blocks, then the first tile's dzA, dzB, x and
+  // gradient-buffer chunks, all issued before the first wait; the weight staging then waits for the weights alone and the
+  // tile's 16 loads stay in flight across it.  Left to itself the scheduler trades this order for registers (it staged the
+  // weights through a rolling window of waits, drained, and issued the tile's loads last): the two scheduling barriers pin it.
+  // per-channel constants of this lane's two channels: the statistics are the channels' (shared), the affine / mean terms per layer
+  float mur[2], rsr[2], gA[2], bA[2], gB[2], bB[2], cA[2][2], cB[2][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = min(n0 + wn * 64 + j * 32 + l31, K - 1);
+    mur[j] = mean[c];
+    rsr[j] = rstd[c];
+    gA[j] = gammaA[c];
+    bA[j] = betaA[c];
+    gB[j] = gammaB[c];
+    bB[j] = betaB[c];
+    cA[j][0] = coefA[2 * c];
+    cA[j][1] = coefA[2 * c + 1];
+    cB[j][0] = coefB[2 * c];
+    cB[j][1] = coefB[2 * c + 1];
+  }
+  __builtin_amdgcn_sched_barrier(0);
   {
     uint4 wa[8], wb[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int k = rr + 16 * i;
-      wa[i] = cok ? *reinterpret_cast<const uint4*>(W1A + (long long)k * ldwA + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
-      wb[i] = cok ? *reinterpret_cast<const uint4*>(W1B + (long long)k * K + n0 + cc * 8) : make_uint4(0u, 0u, 0u, 0u);
+      wa[i] = *reinterpret_cast<const uint4*>(W1A + (long long)k * ldwA + colc);
+      wb[i] = *reinterpret_cast<const uint4*>(W1B + (long long)k * K + colc);
     }
+    load_dzA((long long)blockIdx.x * TMv, true);
+    load_dzB((long long)blockIdx.x * TMv, true);
+    load_x((long long)blockIdx.x * TMv, true);
+    load_g((long long)blockIdx.x * TMv, true);
+    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
       const int k = rr + 16 * i;
       const int f = ((k & 3) << 2) | ((k >> 2) & 3);
-      *reinterpret_cast<uint4*>(wtA + k * 256 + ((cc ^ f) << 4)) = wa[i];
-      *reinterpret_cast<uint4*>(wtB + k * 256 + ((cc ^ f) << 4)) = wb[i];
+      *reinterpret_cast<uint4*>(wtA + k * 256 + ((cc ^ f) << 4)) = keep4(cok, wa[i]);
+      *reinterpret_cast<uint4*>(wtB + k * 256 + ((cc ^ f) << 4)) = keep4(cok, wb[i]);
     }
   }
-  // per-channel constants of this lane's two channels: the statistics are the channels' (shared), the affine / mean terms per layer
   float scA[2], shA[2], scB[2], shB[2], ka[2], kb[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    const int c = n0 + wn * 64 + j * 32 + l31;
-    const bool cv = c < K;
-    const float mu = cv ? mean[c] : 0.0f, rs = cv ? rstd[c] : 0.0f;
-    scA[j] = cv ? gammaA[c] * rs : 0.0f;
-    shA[j] = cv ? fmaf(-mu, scA[j], betaA[c]) : 0.0f;
-    scB[j] = cv ? gammaB[c] * rs : 0.0f;
-    shB[j] = cv ? fmaf(-mu, scB[j], betaB[c]) : 0.0f;
-    const float c1A = cv ? coefA[2 * c] : 0.0f, c2A = cv ? coefA[2 * c + 1] : 0.0f;
-    const float c1B = cv ? coefB[2 * c] : 0.0f, c2B = cv ? coefB[2 * c + 1] : 0.0f;
+    const bool cv = n0 + wn * 64 + j * 32 + l31 < K;
+    const float mu = cv ? mur[j] : 0.0f, rs = cv ? rsr[j] : 0.0f;
+    scA[j] = cv ? gA[j] * rs : 0.0f;
+    shA[j] = cv ? fmaf(-mu, scA[j], bA[j]) : 0.0f;
+    scB[j] = cv ? gB[j] * rs : 0.0f;
+    shB[j] = cv ? fmaf(-mu, scB[j], bB[j]) : 0.0f;
+    const float c1A = cv ? cA[j][0] : 0.0f, c2A = cv ? cA[j][1] : 0.0f;
+    const float c1B = cv ? cB[j][0] : 0.0f, c2B = cv ? cB[j][1] : 0.0f;
     // dx_L = sc_L*(g_L - c1_L - xhat*c2_L) = sc_L*g_L + (ka_L*x + kb_L), as bn1_bwd_kernel<1>; the two affine parts added
     const float kaA = -scA[j] * c2A * rs, kaB = -scB[j] * c2B * rs;
     const float kbA = fmaf(-kaA, mu, -scA[j] * c1A), kbB = fmaf(-kaB, mu, -scB[j] * c1B);
@@ -332,13 +411,17 @@ __global__ __launch_bounds__(256, 2) void bn1_dx_pair_kernel(const bf16_t* __res
   };
   for (int rt = blockIdx.x; rt < nrt; rt += gridDim.x) {
     const long long row0 = (long long)rt * TMv;
-    if (rt != (int)blockIdx.x) issue_loads(rt);
-    __syncthreads();   // the previous row tile is done with the shared tile (and, first trip, the weights are staged below)
+    // each register set is refilled for the workgroup's next row tile once its copy is in LDS (dzA, dzB, x) or consumed (the
+    // gradient buffer); behind the last tile a dummy refill from the tile's own first row, as in bn1_bwd_kernel
+    const bool more = rt + (int)gridDim.x < nrt;
+    const long long nbase = more ? row0 + (long long)gridDim.x * TMv : row0;
+    __syncthreads();   // the previous row tile is done with the shared tile (first trip: the weights are staged)
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int r = rr + 16 * i;
-      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = dar[i];
+      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = keep4(row0 + r < S, dar[i]);
     }
+    load_dzA(nbase, more);
     __syncthreads();
     f32x16 accA[2], accB[2];
     product(wtA, accA);
@@ -346,13 +429,16 @@ __global__ __launch_bounds__(256, 2) void bn1_dx_pair_kernel(const bf16_t* __res
 #pragma unroll
     for (int i = 0; i < NL; ++i) {
       const int r = rr + 16 * i;
-      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = dbr[i];
+      *reinterpret_cast<uint4*>(dzt + r * 256 + ((cc ^ (r & 15)) << 4)) = keep4(row0 + r < S, dbr[i]);
     }
+    load_dzB(nbase, more);
     __syncthreads();
     product(wtB, accB);
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < NL; ++i) *reinterpret_cast<uint4*>(xt + (rr + 16 * i) * TN + cc * 8) = xr[i];
+    for (int i = 0; i < NL; ++i)
+      *reinterpret_cast<uint4*>(xt + (rr + 16 * i) * TN + cc * 8) = keep4(cok && row0 + rr + 16 * i < S, xr[i]);
+    load_x(nbase, more);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -387,6 +473,7 @@ __global__ __launch_bounds__(256, 2) void bn1_dx_pair_kernel(const bf16_t* __res
         }
       }
     }
+    load_g(nbase, more);   // the next tile's rows (last tile: this tile's first row): read and written by this workgroup alone
   }
 }
 

@@ -74,6 +74,17 @@ def main():
         zo = torch.empty_like(z)
         zm, zv, zr = (torch.zeros(128, device=dev) for _ in range(3))
         ws1 = torch.empty(L.mcl_dense_conv1x1_workspace_floats(S), device=dev)
+        # the paired dx (round 6): layer A = this one with 32 channels more (C + 32 <= ld at every shape), layer B = this one
+        W1A = ((torch.rand(128, C + 32, generator=g) - 0.5) / 8).to(torch.bfloat16).to(dev)
+        dzB = ((torch.rand(S, 128, generator=g) - 0.5) * 0.2).to(torch.bfloat16).to(dev)
+        coefA = torch.zeros(2 * (C + 32), device=dev)
+        kprev = torch.zeros(2 * C, device=dev)
+
+        def dx_window_pair():
+            rc = L.mcl_dense_bn1_dx_window(P(dz), P(W1A), C + 32, C, 32, P(xw), ld, S, P(gam), P(bet), P(mu), P(rs), P(coefA),
+                                           P(gw), ld, st())
+            return rc or L.mcl_dense_bn1_dx_pair(P(dz), P(W1A), C + 32, P(gam), P(bet), P(coefA), P(dzB), P(W1), P(gam), P(bet),
+                                                 P(coef), C, P(xw), ld, S, P(mu), P(rs), P(gw), ld, st())
         calls = {
             "conv1x1_fwd (+finalize)": (lambda: L.mcl_dense_conv1x1_fwd(P(x), ld, S, C, P(gam), P(bet), P(mu), P(rs), P(W1), P(zo),
                                                                        128, P(ws1), 1e-5, P(zm), P(zv), P(zr), st()),
@@ -86,6 +97,10 @@ def main():
                                              2 * S * (128 + C)),
             "bn1_dx": (lambda: L.mcl_dense_bn1_dx(P(dz), P(W1), C, P(x), ld, S, P(gam), P(bet), P(mu), P(rs), P(coef), P(gbuf),
                                                   ld, st()), 2 * S * (128 + 3 * C)),
+            "bn1_dx_window + bn1_dx_pair": (dx_window_pair, 2 * S * (128 + 3 * 32) + 2 * S * (256 + 3 * C)),
+            "bn1_dx_sums (+finalize)": (lambda: L.mcl_dense_bn1_dx_sums(P(dz), P(W1), C, P(x), ld, S, P(gam), P(bet), P(mu), P(rs),
+                                                                        P(ws), P(dg), P(db), 1, P(kprev), 1, P(gbuf), ld, st()),
+                                        2 * S * (128 + 3 * C)),
             "r01 bn1_bwd (reduce+fin+dx)": (lambda: L.mcl_dense_bn1_bwd(P(dz), P(W1), C, P(x), ld, S, P(gam), P(bet), P(mu), P(rs),
                                                                         P(ws), P(dg), P(db), 1, P(gbuf), ld, st()),
                                             2 * S * (128 + C) + 2 * S * (128 + 3 * C)),
