@@ -30,10 +30,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, evaluate, ops, retrieval
+from . import evaluate, retrieval
 from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, device, empty, matrix, paired_offsets, stack_rows, upload,
                       validate_offsets, write_json)
-from ._lib import check
+from ._lib import call
 
 N_TOP = 50
 METHOD_TOP_K = {"simple": 1, "average": 50, "weighted_average": 50}          # the notebook's top_k per method
@@ -71,13 +71,10 @@ def summary_device(pred: Tensor, true: Tensor, offsets: Sequence[int], markers: 
     r_cell = e((rows,), torch.float64)
     gene_sum, gene_var, summary = e((S, G), torch.float64), e((S, G), torch.float64), e((S, 7), torch.float64)
     top_sum, top_var = e((S, n_top), torch.int64), e((S, n_top), torch.int64)
-    lib, st = _lib.lib(), ops._stream()
-    check(lib.mcl_cell_pearson(pred.data_ptr(), pred.stride(0), FLOAT_CODE[pred.dtype], true.data_ptr(), true.stride(0),
-                               FLOAT_CODE[true.dtype], rows, G, r_cell.data_ptr(), st), "mcl_cell_pearson")
-    check(lib.mcl_bleep_summary(true.data_ptr(), true.stride(0), FLOAT_CODE[true.dtype], off_d.data_ptr(), S, G, n_top,
-                                r.data_ptr(), r_cell.data_ptr(), ops._p(mk_d), int(mk.size), gene_sum.data_ptr(),
-                                gene_var.data_ptr(), top_sum.data_ptr(), top_var.data_ptr(), summary.data_ptr(), st),
-          "mcl_bleep_summary")
+    call("mcl_cell_pearson", pred, pred.stride(0), FLOAT_CODE[pred.dtype],
+         true, true.stride(0), FLOAT_CODE[true.dtype], rows, G, r_cell)
+    call("mcl_bleep_summary", true, true.stride(0), FLOAT_CODE[true.dtype], off_d, S, G,
+         n_top, r, r_cell, mk_d, int(mk.size), gene_sum, gene_var, top_sum, top_var, summary)
     return {"r": r, "r_cell": r_cell, "gene_sum": gene_sum, "gene_var": gene_var, "top_sum": top_sum, "top_var": top_var,
             "summary": summary}
 
@@ -203,10 +200,8 @@ def gene_gene_correlation(x: ArrayLike, genes: Sequence[int]) -> np.ndarray:
         xs = matrix(x[:, g], "x", dev, FLOAT_CODE, torch.float64)
     off_d, goff_d = upload(off, dev), upload(np.array([0, m * m], dtype=np.int64), dev)
     mean, gram, corr = e((1, m), torch.float64), e((m * m,), torch.float64), e((m, m), torch.float64)
-    lib, st = _lib.lib(), ops._stream()
-    check(lib.mcl_pca_gram(xs.data_ptr(), xs.stride(0), FLOAT_CODE[xs.dtype], off_d.data_ptr(), 1, m, n, goff_d.data_ptr(),
-                           mean.data_ptr(), gram.data_ptr(), st), "mcl_pca_gram")
-    check(lib.mcl_corr_from_gram(gram.data_ptr(), m, corr.data_ptr(), st), "mcl_corr_from_gram")
+    call("mcl_pca_gram", xs, xs.stride(0), FLOAT_CODE[xs.dtype], off_d, 1, m, n, goff_d, mean, gram)
+    call("mcl_corr_from_gram", gram, m, corr)
     return corr.cpu().numpy()
 
 

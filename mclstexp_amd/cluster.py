@@ -25,9 +25,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _arrays, _lib, ops
+from . import _arrays
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, stack_rows, upload, write_json
-from ._lib import check
+from ._lib import call
 
 N_COMPS = 9          # sc.pp.pca(tmp, n_comps=9), utils.py:71
 MAX_DIM = 64         # D <= 64 and K <= 64 (csrc/cluster.hip)
@@ -74,7 +74,6 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
         raise ValueError(f"n_comps = {n_comps} needs more than {n_comps} spots and genes in every segment "
                          f"(smallest min(spots, genes) = {int(m.min())})")
     dev = device("cluster")
-    lib = _lib.lib()
     xd = matrix(x, "x", dev, FLOAT_CODE, torch.float64)
     S = off.size - 1
     goff, eoff = cumulative_offsets(m * m), cumulative_offsets(m * n_comps)
@@ -83,9 +82,7 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     mean = e((S, G), torch.float64)
     gram = e((int(goff[-1]),), torch.float64)
     max_rows = int(seg.max())
-    st = ops._stream()
-    check(lib.mcl_pca_gram(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
-                           goff_d.data_ptr(), mean.data_ptr(), gram.data_ptr(), st), "mcl_pca_gram")
+    call("mcl_pca_gram", xd, xd.stride(0), FLOAT_CODE[xd.dtype], off_d, S, G, max_rows, goff_d, mean, gram)
     gram_h = gram.cpu().numpy()                      # the one synchronisation of the pipeline
     evec = np.empty((int(eoff[-1]),), dtype=np.float64)
     evals = np.empty((S, n_comps), dtype=np.float64)
@@ -97,9 +94,8 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     evec_d, eval_d, eoff_d = upload(evec, dev), upload(evals, dev), upload(eoff, dev)
     loadings = e((S * G * n_comps,), torch.float64)
     sign, z = e((S, n_comps), torch.float64), e((rows, n_comps), torch.float64)
-    check(lib.mcl_pca_project(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], off_d.data_ptr(), S, G, max_rows,
-                              n_comps, mean.data_ptr(), evec_d.data_ptr(), eoff_d.data_ptr(), eval_d.data_ptr(),
-                              loadings.data_ptr(), sign.data_ptr(), z.data_ptr(), st), "mcl_pca_project")
+    call("mcl_pca_project", xd, xd.stride(0), FLOAT_CODE[xd.dtype], off_d, S,
+         G, max_rows, n_comps, mean, evec_d, eoff_d, eval_d, loadings, sign, z)
     return {"scores": z, "sign": sign, "explained_variance": np.maximum(evals, 0.0) / (seg[:, None] - 1.0),
             "offsets": off}
 
@@ -185,7 +181,6 @@ def kmeans(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequenc
     if R < 1 or R > 65535:
         raise ValueError(f"the number of restarts must lie in 1 .. 65535, got {R}")
     dev = device("cluster")
-    lib = _lib.lib()
     zd = matrix(z, "z", dev, FLOAT_CODE, torch.float64)
     if zd.dtype != torch.float64:
         raise ValueError("z must be float64 (the PCA scores are)")
@@ -198,13 +193,10 @@ def kmeans(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequenc
            "centers": e((S, k_max, D), torch.float64), "inertia": e((S,), torch.float64),
            "n_iter": e((S,), torch.int32), "restart": e((S,), torch.int32)}
     work = e((R * rows,), torch.float64)
-    check(lib.mcl_kmeans(zd.data_ptr(), zd.stride(0), off_d.data_ptr(), S, rows, D, ks_d.data_ptr(), k_max, R,
-                         seeds_d.data_ptr() if seeds_d is not None else None, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                         int(segment_base), float(tol), int(max_iter), res["seed_rows"].data_ptr(),
-                         res["labels_all"].data_ptr(), res["centers_all"].data_ptr(), res["inertia_all"].data_ptr(),
-                         res["n_iter_all"].data_ptr(), work.data_ptr(), res["labels"].data_ptr(),
-                         res["centers"].data_ptr(), res["inertia"].data_ptr(), res["n_iter"].data_ptr(),
-                         res["restart"].data_ptr(), ops._stream()), "mcl_kmeans")
+    call("mcl_kmeans", zd, zd.stride(0), off_d, S, rows, D, ks_d, k_max, R, seeds_d,
+         int(seed) & 0xFFFFFFFFFFFFFFFF, int(segment_base), float(tol), int(max_iter), res["seed_rows"],
+         res["labels_all"], res["centers_all"], res["inertia_all"], res["n_iter_all"], work,
+         res["labels"], res["centers"], res["inertia"], res["n_iter"], res["restart"])
     return res
 
 
@@ -219,14 +211,12 @@ def cluster_scores(labels_a: ArrayLike, labels_b: ArrayLike,
         raise ValueError(f"label vectors differ in length: {na} and {nb}")
     off = validate_offsets(offsets, na)
     dev = device("cluster")
-    lib = _lib.lib()
     a = _labels_i32(labels_a, "labels_a", dev)
     b = _labels_i32(labels_b, "labels_b", dev)
     S = off.size - 1
     off_d = upload(off, dev)
     out = torch.empty((S, 2), device=dev, dtype=torch.float64)
-    check(lib.mcl_cluster_scores(a.data_ptr(), b.data_ptr(), off_d.data_ptr(), S, int(np.diff(off).max()),
-                                 out.data_ptr(), ops._stream()), "mcl_cluster_scores")
+    call("mcl_cluster_scores", a, b, off_d, S, int(np.diff(off).max()), out)
     h = out.cpu().numpy()
     return h[:, 0].copy(), h[:, 1].copy()
 

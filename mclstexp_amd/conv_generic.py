@@ -19,16 +19,12 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib, ops
-from ._lib import check
+from . import ops
+from ._lib import call
 
 Tensor = torch.Tensor
 CL = torch.channels_last
 A_KM, B_KM, OUT_F32 = 1, 2, 16           # mcl_gemm_bf16 flags (include/mclstexp_hip.h)
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 def _dt(t: Tensor) -> int:
@@ -59,8 +55,7 @@ def im2col(x: Tensor, k: int, stride: int, pad: int) -> Tensor:
     px, S, _, ld = _rows(x)
     OH, OW = _out_hw(H, W, k, stride, pad)
     cols = torch.empty((B * OH * OW, k * k * C), device=x.device, dtype=x.dtype)
-    check(_lib.lib().mcl_im2col_nhwc(px, ld, B, H, W, C, k, k, stride, pad, _dt(x), cols.data_ptr(), _stream()),
-          "mcl_im2col_nhwc")
+    call("mcl_im2col_nhwc", px, ld, B, H, W, C, k, k, stride, pad, _dt(x), cols)
     return cols
 
 
@@ -71,8 +66,7 @@ def col2im(dcols: Tensor, shape, k: int, stride: int, pad: int, out: Optional[Te
         out = torch.empty((B, C, H, W), device=dcols.device, dtype=dcols.dtype, memory_format=CL)
     po, S, Co, ld = _rows(out)
     assert Co == C and out.dtype == dcols.dtype
-    check(_lib.lib().mcl_col2im_nhwc(dcols.data_ptr(), B, H, W, C, k, k, stride, pad, _dt(dcols), po, ld, int(accumulate),
-                                     _stream()), "mcl_col2im_nhwc")
+    call("mcl_col2im_nhwc", dcols, B, H, W, C, k, k, stride, pad, _dt(dcols), po, ld, accumulate)
     return out
 
 
@@ -80,16 +74,14 @@ def _gemm(A: Tensor, a_ptr: int, lda: int, a_km: bool, B: Tensor, b_ptr: int, ld
           ldc: int, M: int, N: int, K: int, out_f32: bool = False, accumulate: bool = False, ksplit: int = 1) -> None:
     """C (M x N) (+)= A (M x K) . B (K x N) on the GEMM of the operands' dtype.  ``a_km``: A stored [K][M] (reduction-major),
     else [M][K]; ``b_km``: B stored [K][N], else [N][K]."""
-    L = _lib.lib()
     if A.dtype == torch.bfloat16:
         flags = (A_KM if a_km else 0) | (B_KM if b_km else 0) | (OUT_F32 if out_f32 else 0)
         ws = None
         if ksplit > 1:
             from .densenet_fused import _ws
-            ws = _ws(L.mcl_gemm_bf16_workspace_floats(M, ldc, ksplit), C.device)
-        check(L.mcl_gemm_bf16(a_ptr, lda, 0, b_ptr, ldb, 0, c_ptr, ldc, 0, M, N, K, 1, 1, 0, 0, 0, 1.0, flags, None, None, 0, 0,
-                              None, 0, None, 0, ksplit, None if ws is None else ws.data_ptr(), int(accumulate), _stream()),
-              "mcl_gemm_bf16")
+            ws = _ws(call("mcl_gemm_bf16_workspace_floats", M, ldc, ksplit), C.device)
+        call("mcl_gemm_bf16", a_ptr, lda, 0, b_ptr, ldb, 0, c_ptr, ldc, 0, M, N, K, 1, 1, 0,
+             0, 0, 1.0, flags, None, None, 0, 0, None, 0, None, 0, ksplit, ws, accumulate)
         return
     # fp32: mcl_gemm with explicit element strides (exact fp32 MFMA); split-K is chosen inside gemm_raw
     sAm, sAk = (1, lda) if a_km else (lda, 1)
@@ -154,7 +146,7 @@ def conv_bwd_data(dy: Tensor, wk: Tensor, x_shape, stride: int, pad: int) -> Ten
         dyc = im2col(dy, k, 1, pad)                                       # (S, k*k*Co), columns (ky, kx, co)
         # (Ci, k, k, Co): wf[ci,ky,kx,co] = w[co,k-1-ky,k-1-kx,ci] -- one own launch (was permute + flip + contiguous on ATen)
         wf = torch.empty((Ci, k * k * Co), device=dy.device, dtype=dy.dtype)
-        check(_lib.lib().mcl_weight_rot180(wk.data_ptr(), wf.data_ptr(), Co, k, Ci, _dt(dy), _stream()), "mcl_weight_rot180")
+        call("mcl_weight_rot180", wk, wf, Co, k, Ci, _dt(dy))
         dx = torch.empty((B, Ci, H, W), device=dy.device, dtype=dy.dtype, memory_format=CL)
         _gemm(dyc, dyc.data_ptr(), k * k * Co, False, wf, wf.data_ptr(), k * k * Co, False, dx, dx.data_ptr(), Ci, S, Ci, k * k * Co)
         return dx
@@ -256,8 +248,7 @@ class MaxPool3s2Fn(torch.autograd.Function):
         B, C, H, W = x.shape
         y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=x.dtype, memory_format=CL)
         idx = torch.empty((B, y.shape[2], y.shape[3], C), device=x.device, dtype=torch.uint8)
-        check(_lib.lib().mcl_maxpool3s2_nhwc_fwd_any(x.data_ptr(), y.data_ptr(), idx.data_ptr(), B, H, W, C, _dt(x), _stream()),
-              "mcl_maxpool3s2_nhwc_fwd_any")
+        call("mcl_maxpool3s2_nhwc_fwd_any", x, y, idx, B, H, W, C, _dt(x))
         ctx.save_for_backward(idx)
         ctx.shape = (B, C, H, W)
         return y
@@ -268,8 +259,7 @@ class MaxPool3s2Fn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         dy = _dense_cl(dy)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=dy.dtype, memory_format=CL)
-        check(_lib.lib().mcl_maxpool3s2_nhwc_bwd_any(idx.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, H, W, C, _dt(dy),
-                                                     _stream()), "mcl_maxpool3s2_nhwc_bwd_any")
+        call("mcl_maxpool3s2_nhwc_bwd_any", idx, dy, dx, B, H, W, C, _dt(dy))
         return dx
 
 
@@ -281,8 +271,7 @@ class AvgPool2Fn(torch.autograd.Function):
         x = _dense_cl(x)
         B, C, H, W = x.shape
         y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=x.dtype, memory_format=CL)
-        check(_lib.lib().mcl_avgpool2_nhwc_any(x.data_ptr(), y.data_ptr(), B, H, W, C, 0, _dt(x), _stream()),
-              "mcl_avgpool2_nhwc_any")
+        call("mcl_avgpool2_nhwc_any", x, y, B, H, W, C, 0, _dt(x))
         ctx.shape = (B, C, H, W)
         return y
 
@@ -291,8 +280,7 @@ class AvgPool2Fn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         dy = _dense_cl(dy)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=dy.dtype, memory_format=CL)
-        check(_lib.lib().mcl_avgpool2_nhwc_any(dy.data_ptr(), dx.data_ptr(), B, H, W, C, 1, _dt(dy), _stream()),
-              "mcl_avgpool2_nhwc_any")
+        call("mcl_avgpool2_nhwc_any", dy, dx, B, H, W, C, 1, _dt(dy))
         return dx
 
 
@@ -304,7 +292,7 @@ class GlobalAvgPoolFn(torch.autograd.Function):
         B, C, H, W = x.shape
         px, S, _, ld = _rows(x)
         out = torch.empty((B, C), device=x.device, dtype=torch.float32)
-        check(_lib.lib().mcl_gap_nhwc_fwd(px, ld, B, H * W, C, _dt(x), out.data_ptr(), _stream()), "mcl_gap_nhwc_fwd")
+        call("mcl_gap_nhwc_fwd", px, ld, B, H * W, C, _dt(x), out)
         ctx.shape, ctx.dt = (B, C, H, W), x.dtype
         return out
 
@@ -313,8 +301,7 @@ class GlobalAvgPoolFn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         g = g.contiguous().float()
         dx = torch.empty((B, C, H, W), device=g.device, dtype=ctx.dt, memory_format=CL)
-        check(_lib.lib().mcl_gap_nhwc_bwd(g.data_ptr(), B, H * W, C, 0 if ctx.dt == torch.float32 else 1, dx.data_ptr(),
-                                          _stream()), "mcl_gap_nhwc_bwd")
+        call("mcl_gap_nhwc_bwd", g, B, H * W, C, 0 if ctx.dt == torch.float32 else 1, dx)
         return dx
 
 
@@ -325,7 +312,7 @@ class AddReluFn(torch.autograd.Function):
     def forward(ctx, a, b):
         a, b = _dense_cl(a), _dense_cl(b)
         y = torch.empty_like(a, memory_format=CL)
-        check(_lib.lib().mcl_add_relu(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), 0, _dt(a), _stream()), "mcl_add_relu")
+        call("mcl_add_relu", a, b, y, a.numel(), 0, _dt(a))
         ctx.save_for_backward(y)
         return y
 
@@ -334,8 +321,7 @@ class AddReluFn(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         dy = _dense_cl(dy)
         dx = torch.empty_like(y, memory_format=CL)
-        check(_lib.lib().mcl_add_relu(dy.data_ptr(), y.data_ptr(), dx.data_ptr(), y.numel(), 1, _dt(y), _stream()),
-              "mcl_add_relu (backward)")
+        call("mcl_add_relu", dy, y, dx, y.numel(), 1, _dt(y))
         return dx, dx
 
 
@@ -351,8 +337,7 @@ class Fork2Fn(torch.autograd.Function):
     def backward(ctx, g1, g2):
         g1, g2 = _dense_cl(g1), _dense_cl(g2)
         out = torch.empty_like(g1, memory_format=CL)
-        check(_lib.lib().mcl_add_relu(g1.data_ptr(), g2.data_ptr(), out.data_ptr(), g1.numel(), 2, _dt(g1), _stream()),
-              "mcl_add_relu (plain add)")
+        call("mcl_add_relu", g1, g2, out, g1.numel(), 2, _dt(g1))
         return out
 
 

@@ -33,8 +33,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from . import _lib
-from ._lib import check
+from ._lib import call, current_stream
 
 Tensor = torch.Tensor
 CL = torch.channels_last
@@ -54,8 +53,7 @@ def reset_fallbacks() -> None:
     _fallbacks.clear()
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+_stream = current_stream                 # (tests and tools that call the C ABI directly pass it)
 
 
 # ---- MCL_STAMPS=1: GPU wall-clock stamps at labelled points of the step (a one-thread kernel on the CURRENT stream, captured
@@ -78,7 +76,7 @@ def stamp(label: str) -> None:
     else:
         _stamp_labels.append(label)
         idx = len(_stamp_labels) - 1
-    check(_lib.lib().mcl_stamp(buf.data_ptr(), idx, _stream()), "mcl_stamp")
+    call("mcl_stamp", buf, idx)
 
 
 def read_stamps() -> dict:
@@ -128,7 +126,7 @@ def dense_cl(t: Tensor) -> Tensor:
         return t.contiguous(memory_format=CL)
     out = torch.empty((B, C, H, W), device=t.device, dtype=t.dtype, memory_format=CL)
     es = t.element_size()
-    check(_lib.lib().mcl_copy_rows(t.data_ptr(), ld * es, out.data_ptr(), C * es, B * H * W, C * es, _stream()), "mcl_copy_rows")
+    call("mcl_copy_rows", t, ld * es, out, C * es, B * H * W, C * es)
     return out
 
 
@@ -144,25 +142,19 @@ def _ws(nfloats: int, device) -> Tensor:
 def bn_stats(x: Tensor, mean: Tensor, var: Tensor, rstd: Tensor, eps: float, copy_out: Optional[Tensor] = None):
     p, S, C, ld = _rows(x)
     dt = _dt(x)
-    L = _lib.lib()
-    n = L.mcl_bn_workspace_floats(S, C, dt)
-    if n < 0:
-        raise RuntimeError(f"mcl_bn_workspace_floats rejected S={S} C={C} dtype={dt}")
-    ws = _ws(n, x.device)
+    ws = _ws(call("mcl_bn_workspace_floats", S, C, dt), x.device)
     po, ldo = (None, 0)
     if copy_out is not None:
         po, S2, C2, ldo = _rows(copy_out)
         assert (S2, C2) == (S, C) and copy_out.dtype == x.dtype
-    check(L.mcl_bn_stats(p, ld, S, C, dt, po, ldo, ws.data_ptr(), eps, mean.data_ptr(), var.data_ptr(),
-                         rstd.data_ptr(), _stream()), "mcl_bn_stats")
+    call("mcl_bn_stats", p, ld, S, C, dt, po, ldo, ws, eps, mean, var, rstd)
 
 
 def bn_act_fwd(x: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, rstd: Tensor, relu: bool, out: Tensor):
     p, S, C, ld = _rows(x)
     po, S2, C2, ldo = _rows(out)
     assert (S2, C2) == (S, C) and out.dtype == x.dtype
-    check(_lib.lib().mcl_bn_act_fwd(p, ld, S, C, _dt(x), gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-                                    rstd.data_ptr(), int(relu), po, ldo, _stream()), "mcl_bn_act_fwd")
+    call("mcl_bn_act_fwd", p, ld, S, C, _dt(x), gamma, beta, mean, rstd, relu, po, ldo)
 
 
 def _has_grad_hooks(p: Tensor) -> bool:
@@ -220,16 +212,14 @@ def bn_act_bwd(dy: Tensor, x: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor,
     px, S3, C3, ldx = _rows(dx)
     assert (S2, C2) == (S, C) == (S3, C3) and dy.dtype == x.dtype == dx.dtype
     dt = _dt(x)
-    L = _lib.lib()
-    ws = _ws(L.mcl_bn_workspace_floats(S, C, dt), x.device)
+    ws = _ws(call("mcl_bn_workspace_floats", S, C, dt), x.device)
     if into_param_grads:
         dg, db = gamma.grad, beta.grad
     else:
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
-    check(L.mcl_bn_act_bwd(pd, ldd, p, ld, S, C, dt, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-                           rstd.data_ptr(), int(relu), ws.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                           int(into_param_grads), px, ldx, int(accumulate), _stream()), "mcl_bn_act_bwd")
+    call("mcl_bn_act_bwd", pd, ldd, p, ld, S, C, dt, gamma, beta, mean,
+         rstd, relu, ws, dg, db, into_param_grads, px, ldx, accumulate)
     return (None, None) if into_param_grads else (dg, db)
 
 
@@ -303,7 +293,7 @@ class _RunningStats:
             if (bn.running_mean.dtype != torch.float32 or not bn.running_mean.is_contiguous()
                     or not bn.running_var.is_contiguous() or not t.is_contiguous() or bn.running_mean.device != t.device):
                 raise RuntimeError("densenet_fused: BatchNorm running statistics must be contiguous fp32 on the GPU")
-        check(_lib.lib().mcl_bn_running_update(n, rm, rv, mean, var, nbt, cs, fac, mom, _stream()), "mcl_bn_running_update")
+        call("mcl_bn_running_update", n, rm, rv, mean, var, nbt, cs, fac, mom)
         self.mods, self.means, self.vars, self.factors = [], [], [], []
 
 
@@ -340,12 +330,8 @@ def dense_conv1x1_fwd(x: Tensor, g1: Tensor, b1: Tensor, mean: Tensor, rstd: Ten
     px, S, K, ldx = _rows(x)
     B, _, H, W = x.shape
     z = torch.empty((B, 128, H, W), device=x.device, dtype=torch.bfloat16, memory_format=CL)
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_conv1x1_workspace_floats(S), x.device)
-    nz = (lambda t: None if t is None else t.data_ptr())
-    check(L.mcl_dense_conv1x1_fwd(px, ldx, S, K, g1.data_ptr(), b1.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                  w16.data_ptr(), z.data_ptr(), 128, ws.data_ptr(), eps2, nz(zmean),
-                                  nz(zvar), nz(zrstd), _stream()), "mcl_dense_conv1x1_fwd")
+    ws = _ws(call("mcl_dense_conv1x1_workspace_floats", S), x.device)
+    call("mcl_dense_conv1x1_fwd", px, ldx, S, K, g1, b1, mean, rstd, w16, z, 128, ws, eps2, zmean, zvar, zrstd)
     return z
 
 
@@ -359,16 +345,13 @@ def dense_bn1_bwd(dz: Tensor, w16: Tensor, x: Tensor, g1: Tensor, b1: Tensor, me
     px, S, C, ldx = _rows(x)
     pg, S2, C2, ldg = _rows(gbuf)
     assert (S2, C2) == (S, C) and dz.is_contiguous(memory_format=CL) and dz.shape[1] == 128
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_bn1_bwd_workspace_floats(S, C), x.device)
+    ws = _ws(call("mcl_dense_bn1_bwd_workspace_floats", S, C), x.device)
     if into_param_grads:
         dg, db = g1.grad, b1.grad
     else:
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
-    check(L.mcl_dense_bn1_bwd(dz.data_ptr(), w16.data_ptr(), C, px, ldx, S, g1.data_ptr(), b1.data_ptr(),
-                              mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                              int(into_param_grads), pg, ldg, _stream()), "mcl_dense_bn1_bwd")
+    call("mcl_dense_bn1_bwd", dz, w16, C, px, ldx, S, g1, b1, mean, rstd, ws, dg, db, into_param_grads, pg, ldg)
     return (None, None) if into_param_grads else (dg, db)
 
 
@@ -380,17 +363,14 @@ def dense_bn1_dx_sums(dz: Tensor, w16: Tensor, x: Tensor, g1: Tensor, b1: Tensor
     px, S, C, ldx = _rows(x)
     pg, S2, C2, ldg = _rows(gbuf)
     assert (S2, C2) == (S, C) and dz.is_contiguous(memory_format=CL) and dz.shape[1] == 128 and kprev.numel() >= 2 * C
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_bn1_bwd_workspace_floats(S, C), x.device)
+    ws = _ws(call("mcl_dense_bn1_bwd_workspace_floats", S, C), x.device)
     if into_param_grads:
         dg, db = g1.grad, b1.grad
     else:
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
-    check(L.mcl_dense_bn1_dx_sums(dz.data_ptr(), w16.data_ptr(), C, px, ldx, S, g1.data_ptr(), b1.data_ptr(),
-                                  mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                  int(into_param_grads), kprev.data_ptr(), int(have_prev), pg, ldg, _stream()),
-          "mcl_dense_bn1_dx_sums")
+    call("mcl_dense_bn1_dx_sums", dz, w16, C, px, ldx, S, g1, b1, mean,
+         rstd, ws, dg, db, into_param_grads, kprev, have_prev, pg, ldg)
     return (None, None) if into_param_grads else (dg, db)
 
 
@@ -400,8 +380,7 @@ def dense_bn1_fix(buf: Tensor, gbuf: Tensor, c0: int, nc: int, mean: Tensor, rst
     px, S, _, ldx = _rows(buf)
     pg, S2, _, ldg = _rows(gbuf)
     assert S == S2
-    check(_lib.lib().mcl_dense_bn1_fix(px, ldx, pg, ldg, S, c0, nc, mean.data_ptr(), rstd.data_ptr(), kacc.data_ptr(),
-                                       _stream()), "mcl_dense_bn1_fix")
+    call("mcl_dense_bn1_fix", px, ldx, pg, ldg, S, c0, nc, mean, rstd, kacc)
 
 
 # Single-pass BatchNorm-1 backward (each layer's mean terms applied one pass late, one pass over (dz, x) less per layer) on
@@ -440,18 +419,14 @@ def dense_bn1_wrw(dz: Tensor, w16: Tensor, x: Tensor, g1: Tensor, b1: Tensor, me
     BatchNorm-backward means per channel, what the dx pass(es) apply (mcl_dense_bn1_wrw: Gram partials + fixed-order merge)."""
     px, S, C, ldx = _rows(x)
     assert dz.is_contiguous(memory_format=CL) and dz.shape[1] == 128
-    L = _lib.lib()
-    ws = _ws(L.mcl_wrw_workspace_floats(S, 128, C), x.device)
+    ws = _ws(call("mcl_wrw_workspace_floats", S, 128, C), x.device)
     if into_param_grads:
         dg, db = g1.grad, b1.grad
     else:
         dg = torch.empty(C, device=x.device, dtype=torch.float32)
         db = torch.empty(C, device=x.device, dtype=torch.float32)
     coef = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-    check(L.mcl_dense_bn1_wrw(dz.data_ptr(), w16.data_ptr(), C, px, ldx, S, g1.data_ptr(), b1.data_ptr(),
-                              mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), w_param.grad.data_ptr(), 1,
-                              dg.data_ptr(), db.data_ptr(), int(into_param_grads), coef.data_ptr(), _stream()),
-          "mcl_dense_bn1_wrw")
+    call("mcl_dense_bn1_wrw", dz, w16, C, px, ldx, S, g1, b1, mean, rstd, ws, w_param.grad, 1, dg, db, into_param_grads, coef)
     return (None, None, coef) if into_param_grads else (dg, db, coef)
 
 
@@ -461,15 +436,11 @@ def dense_bn1_dx(dz: Tensor, w16: Tensor, x: Tensor, g1: Tensor, b1: Tensor, mea
     px, S, C, ldx = _rows(x)
     pg, S2, C2, ldg = _rows(gbuf)
     assert (S2, C2) == (S, C)
-    L = _lib.lib()
     if window is None:
-        check(L.mcl_dense_bn1_dx(dz.data_ptr(), w16.data_ptr(), C, px, ldx, S, g1.data_ptr(), b1.data_ptr(),
-                                 mean.data_ptr(), rstd.data_ptr(), coef.data_ptr(), pg, ldg, _stream()), "mcl_dense_bn1_dx")
+        call("mcl_dense_bn1_dx", dz, w16, C, px, ldx, S, g1, b1, mean, rstd, coef, pg, ldg)
     else:
         c0, nc = window
-        check(L.mcl_dense_bn1_dx_window(dz.data_ptr(), w16.data_ptr(), C, c0, nc, px, ldx, S, g1.data_ptr(), b1.data_ptr(),
-                                        mean.data_ptr(), rstd.data_ptr(), coef.data_ptr(), pg, ldg, _stream()),
-              "mcl_dense_bn1_dx_window")
+        call("mcl_dense_bn1_dx_window", dz, w16, C, c0, nc, px, ldx, S, g1, b1, mean, rstd, coef, pg, ldg)
 
 
 def dense_bn1_dx_pair(A, B, x: Tensor, mean: Tensor, rstd: Tensor, gbuf: Tensor) -> None:
@@ -480,9 +451,7 @@ def dense_bn1_dx_pair(A, B, x: Tensor, mean: Tensor, rstd: Tensor, gbuf: Tensor)
     px, S, C, ldx = _rows(x)
     pg, S2, C2, ldg = _rows(gbuf)
     assert (S2, C2) == (S, C) and wA.shape[1] >= C and wB.shape[1] == C
-    check(_lib.lib().mcl_dense_bn1_dx_pair(dzA.data_ptr(), wA.data_ptr(), wA.shape[1], gA.data_ptr(), bA.data_ptr(), cA.data_ptr(),
-                                           dzB.data_ptr(), wB.data_ptr(), gB.data_ptr(), bB.data_ptr(), cB.data_ptr(), C, px, ldx, S,
-                                           mean.data_ptr(), rstd.data_ptr(), pg, ldg, _stream()), "mcl_dense_bn1_dx_pair")
+    call("mcl_dense_bn1_dx_pair", dzA, wA, wA.shape[1], gA, bA, cA, dzB, wB, gB, bB, cB, C, px, ldx, S, mean, rstd, pg, ldg)
 
 
 # conv2 (3x3) backward-data + norm2/relu2 backward (csrc/dense_bwd.hip): dy is read in place from the gradient buffer
@@ -502,8 +471,7 @@ def dense_conv3x3_bwd(dy: Tensor, w16: Tensor, z: Tensor, g2: Tensor, b2: Tensor
     B, C, H, W = z.shape
     pd, S, Co, lddy = _rows(dy)
     assert C == 128 and Co == 32 and S == B * H * W and z.is_contiguous(memory_format=CL)
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_conv3x3_bwd_workspace_floats(S), z.device)
+    ws = _ws(call("mcl_dense_conv3x3_bwd_workspace_floats", S), z.device)
     scratch = torch.empty_like(z, memory_format=CL)
     dz = torch.empty_like(z, memory_format=CL)
     if into_param_grads:
@@ -517,16 +485,10 @@ def dense_conv3x3_bwd(dy: Tensor, w16: Tensor, z: Tensor, g2: Tensor, b2: Tensor
         pxf, S2, C2, ldxf = _rows(xf)
         assert (S2, C2) == (S, 32) and fk.is_contiguous() and fk.numel() == 64
         dyc = torch.empty((B, 32, H, W), device=z.device, dtype=z.dtype, memory_format=CL)
-        check(L.mcl_dense_conv3x3_bwd_fix(pd, lddy, S, H, W, w16.data_ptr(), z.data_ptr(), g2.data_ptr(), b2.data_ptr(),
-                                          m2.data_ptr(), r2.data_ptr(), ws.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                          int(into_param_grads), scratch.data_ptr(), dz.data_ptr(), pxf, ldxf,
-                                          fm.data_ptr(), fr.data_ptr(), fk.data_ptr(), dyc.data_ptr(), _stream()),
-              "mcl_dense_conv3x3_bwd_fix")
+        call("mcl_dense_conv3x3_bwd_fix", pd, lddy, S, H, W, w16, z, g2, b2, m2, r2,
+             ws, dg, db, into_param_grads, scratch, dz, pxf, ldxf, fm, fr, fk, dyc)
     else:
-        check(L.mcl_dense_conv3x3_bwd(pd, lddy, S, H, W, w16.data_ptr(), z.data_ptr(), g2.data_ptr(), b2.data_ptr(),
-                                      m2.data_ptr(), r2.data_ptr(), ws.data_ptr(), dg.data_ptr(), db.data_ptr(),
-                                      int(into_param_grads), scratch.data_ptr(), dz.data_ptr(), _stream()),
-              "mcl_dense_conv3x3_bwd")
+        call("mcl_dense_conv3x3_bwd", pd, lddy, S, H, W, w16, z, g2, b2, m2, r2, ws, dg, db, into_param_grads, scratch, dz)
     return (dz, None, None, dyc) if into_param_grads else (dz, dg, db, dyc)
 
 
@@ -539,12 +501,8 @@ def dense_conv3x3_fwd(z: Tensor, g2: Tensor, b2: Tensor, m2: Tensor, r2: Tensor,
     B, C, H, W = z.shape
     po, S, Co, ldo = _rows(out)
     assert C == 128 and Co == 32 and z.is_contiguous(memory_format=CL) and S == B * H * W
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_conv3x3_workspace_floats(S), z.device)
-    nz = (lambda t: None if t is None else t.data_ptr())
-    check(L.mcl_dense_conv3x3_fwd(z.data_ptr(), S, H, W, g2.data_ptr(), b2.data_ptr(), m2.data_ptr(), r2.data_ptr(),
-                                  w16.data_ptr(), po, ldo, ws.data_ptr(), eps, nz(ymean), nz(yvar),
-                                  nz(yrstd), _stream()), "mcl_dense_conv3x3_fwd")
+    ws = _ws(call("mcl_dense_conv3x3_workspace_floats", S), z.device)
+    call("mcl_dense_conv3x3_fwd", z, S, H, W, g2, b2, m2, r2, w16, po, ldo, ws, eps, ymean, yvar, yrstd)
 
 
 def _grad_target_khwc(w_param: Tensor) -> Tuple[Tensor, bool]:
@@ -571,13 +529,10 @@ def dense_conv3x3_wrw(dy: Tensor, z: Tensor, g2: Tensor, b2: Tensor, m2: Tensor,
     B, C, H, W = z.shape
     pd, S, Co, lddy = _rows(dy)
     assert Co == 32 and S == B * H * W
-    L = _lib.lib()
     tgt, in_place = _grad_target_khwc(w_param)
     # the side stream has its own workspace (keyed by stream in _ws): no aliasing with the main chain's
-    ws = _ws(L.mcl_dense_conv3x3_wrw_workspace_floats(S), z.device)
-    check(L.mcl_dense_conv3x3_wrw_det(pd, lddy, z.data_ptr(), S, H, W, g2.data_ptr(), b2.data_ptr(), m2.data_ptr(),
-                                      r2.data_ptr(), ws.data_ptr(), tgt.data_ptr(), int(in_place), _stream()),
-          "mcl_dense_conv3x3_wrw_det")
+    ws = _ws(call("mcl_dense_conv3x3_wrw_workspace_floats", S), z.device)
+    call("mcl_dense_conv3x3_wrw_det", pd, lddy, z, S, H, W, g2, b2, m2, r2, ws, tgt, in_place)
     _grad_finish_khwc(w_param, tgt, in_place)
     return True
 
@@ -612,11 +567,9 @@ def conv1x1_wrw(dz: Tensor, a: Tensor, w_param: Tensor, bn=None) -> Optional[Ten
     else:
         tgt = torch.zeros((M, N, 1, 1), device=dz.device, dtype=torch.float32)
         ret = tgt
-    g_, b_, m_, r_ = (t.data_ptr() for t in bn) if bn is not None else (None, None, None, None)
-    L = _lib.lib()
-    ws = _ws(L.mcl_wrw_workspace_floats(S, min(M, 128), N), dz.device)
-    check(L.mcl_conv1x1_wrw_det(pz, ldz, pa, lda, g_, b_, m_, r_, ws.data_ptr(), tgt.data_ptr(), 1, S, M, N,
-                                _stream()), "mcl_conv1x1_wrw_det")
+    g_, b_, m_, r_ = bn if bn is not None else (None, None, None, None)
+    ws = _ws(call("mcl_wrw_workspace_floats", S, min(M, 128), N), dz.device)
+    call("mcl_conv1x1_wrw_det", pz, ldz, pa, lda, g_, b_, m_, r_, ws, tgt, 1, S, M, N)
     return ret
 
 
@@ -641,8 +594,7 @@ def _wgrad(w: Tensor, dw: Tensor) -> Optional[Tensor]:
     if _direct_all(w) and _same_order(dw, w.grad) and dw.dtype in (
             torch.bfloat16, torch.float32):
         # (a mixed-dtype torch add_ on the channels-last strided view costs 45 us per weight)
-        check(_lib.lib().mcl_accum_into_f32(w.grad.data_ptr(), dw.data_ptr(), dw.numel(), _dt(dw), _stream()),
-              "mcl_accum_into_f32")
+        call("mcl_accum_into_f32", w.grad, dw, dw.numel(), _dt(dw))
         return None
     return dw.to(w.dtype)
 
@@ -667,8 +619,7 @@ def cast_dense_bf16(w: Tensor) -> Optional[Tensor]:
     if not dense:
         return None
     out = torch.empty_strided(w.shape, w.stride(), device=w.device, dtype=torch.bfloat16)
-    check(_lib.lib().mcl_cast_f32_to_bf16(w.data_ptr(), w.numel(), out.data_ptr(), w.numel(), 1, w.numel(), _stream()),
-          "mcl_cast_f32_to_bf16")
+    call("mcl_cast_f32_to_bf16", w, w.numel(), out, w.numel(), 1, w.numel())
     return out
 
 
@@ -804,9 +755,6 @@ SEAM_MAX_SPINS = 0
 # phase stamps; None (the default) = off.  Passed per call: the library keeps no state.
 BLOCK_STAMPS: Optional[Tensor] = None
 
-
-def _stamps_ptr():
-    return BLOCK_STAMPS.data_ptr() if BLOCK_STAMPS is not None else None
 _cu_count: dict = {}
 
 
@@ -862,7 +810,6 @@ def dense_block_bwd_persistent(buf: Tensor, gbuf: Tensor, params, wcast, zs, sta
     import ctypes as C
     B, Ct, H, W = buf.shape
     dev = buf.device
-    Lb = _lib.lib()
     dzs = [torch.empty((B, 128, H, W), device=dev, dtype=torch.bfloat16, memory_format=CL) for _ in range(L)]
     dycs = [torch.empty((B, 32, H, W), device=dev, dtype=torch.bfloat16, memory_format=CL) for _ in range(L)]
     n1 = [128 * (C0 + 32 * l) for l in range(L)]
@@ -874,11 +821,9 @@ def dense_block_bwd_persistent(buf: Tensor, gbuf: Tensor, params, wcast, zs, sta
         o += n
     o2 = [o + l * n2 for l in range(L)]
     vp = C.c_void_p * L
-    check(Lb.mcl_dense_block_pack_bwd(vp(*[wcast[2 * l].data_ptr() for l in range(L)]),
-                                      vp(*[wcast[2 * l + 1].data_ptr() for l in range(L)]),
-                                      vp(*[packed.data_ptr() + 2 * o1[l] for l in range(L)]),
-                                      vp(*[packed.data_ptr() + 2 * o2[l] for l in range(L)]), L, C0, _stream()),
-          "mcl_dense_block_pack_bwd")
+    call("mcl_dense_block_pack_bwd", vp(*[wcast[2 * l].data_ptr() for l in range(L)]),
+         vp(*[wcast[2 * l + 1].data_ptr() for l in range(L)]), vp(*[packed.data_ptr() + 2 * o1[l] for l in range(L)]),
+         vp(*[packed.data_ptr() + 2 * o2[l] for l in range(L)]), L, C0)
     ptrs = []
     for l in range(L):
         g1, b1, _, g2, b2, _ = params[6 * l: 6 * l + 6]
@@ -887,7 +832,7 @@ def dense_block_bwd_persistent(buf: Tensor, gbuf: Tensor, params, wcast, zs, sta
                  packed.data_ptr() + 2 * o2[l], zs[l].data_ptr(), m2.data_ptr(), r2.data_ptr(), dzs[l].data_ptr(),
                  dycs[l].data_ptr(), g1.grad.data_ptr(), b1.grad.data_ptr(), g2.grad.data_ptr(), b2.grad.data_ptr()]
     arr = (C.c_void_p * len(ptrs))(*ptrs)
-    nbytes = Lb.mcl_dense_block_bwd_workspace_bytes(B, L)
+    nbytes = call("mcl_dense_block_bwd_workspace_bytes", B, L)
     ws = _ws((nbytes + 255 + 3) // 4 + 64, dev)
     base = (ws.data_ptr() + 255) & ~255
     from . import ops as _ops
@@ -896,8 +841,7 @@ def dense_block_bwd_persistent(buf: Tensor, gbuf: Tensor, params, wcast, zs, sta
     pg, S2, C2, ldg = _rows(gbuf)
     if ld != Ct or ldg != Ct:
         raise RuntimeError("dense_block_bwd_persistent: the concat and gradient buffers must be dense channels-last")
-    check(Lb.mcl_dense_block_bwd(px, pg, B, H, W, Ct, C0, L, arr, stats.mean.data_ptr(), stats.rstd.data_ptr(), base,
-                                 err.data_ptr(), SEAM_MAX_SPINS, _stamps_ptr(), _stream()), "mcl_dense_block_bwd")
+    call("mcl_dense_block_bwd", px, pg, B, H, W, Ct, C0, L, arr, stats.mean, stats.rstd, base, err, SEAM_MAX_SPINS, BLOCK_STAMPS)
     return dzs, dycs
 
 
@@ -908,7 +852,6 @@ def dense_block_fwd_persistent(buf: Tensor, params, wcast, stats: "_BlockStats",
     import ctypes as C
     B, Ct, H, W = buf.shape
     dev = buf.device
-    Lb = _lib.lib()
     zs = [torch.empty((B, 128, H, W), device=dev, dtype=torch.bfloat16, memory_format=CL) for _ in range(L)]
     # conv1 weights in the kernel's streaming order (one launch per call: the weights change every step)
     sizes = [128 * (C0 + 32 * l) for l in range(L)]
@@ -923,7 +866,7 @@ def dense_block_fwd_persistent(buf: Tensor, params, wcast, stats: "_BlockStats",
             raise RuntimeError("dense_block_fwd_persistent: weights must be channels-last / (N, K) row-major")
     src = (C.c_void_p * L)(*[wcast[2 * l].data_ptr() for l in range(L)])
     dst = (C.c_void_p * L)(*[packed.data_ptr() + 2 * offs[l] for l in range(L)])
-    check(Lb.mcl_dense_block_pack_w1(src, dst, L, C0, _stream()), "mcl_dense_block_pack_w1")
+    call("mcl_dense_block_pack_w1", src, dst, L, C0)
     ptrs = []
     for l in range(L):
         g1, b1, _, g2, b2, _ = params[6 * l: 6 * l + 6]
@@ -932,7 +875,7 @@ def dense_block_fwd_persistent(buf: Tensor, params, wcast, stats: "_BlockStats",
         ptrs += [g1.data_ptr(), b1.data_ptr(), packed.data_ptr() + 2 * offs[l], g2.data_ptr(), b2.data_ptr(), w2c.data_ptr(),
                  zs[l].data_ptr(), m2.data_ptr(), v2.data_ptr(), r2.data_ptr()]
     arr = (C.c_void_p * len(ptrs))(*ptrs)
-    nbytes = Lb.mcl_dense_block_fwd_workspace_bytes(B, L)
+    nbytes = call("mcl_dense_block_fwd_workspace_bytes", B, L)
     ws = _ws((nbytes + 255 + 3) // 4 + 64, dev)
     base = (ws.data_ptr() + 255) & ~255
     from . import ops as _ops
@@ -940,8 +883,8 @@ def dense_block_fwd_persistent(buf: Tensor, params, wcast, stats: "_BlockStats",
     px, S, C_, ld = _rows(buf)
     if ld != Ct:
         raise RuntimeError("dense_block_fwd_persistent: the concat buffer must be dense channels-last")
-    check(Lb.mcl_dense_block_fwd(px, B, H, W, Ct, C0, L, arr, eps1, eps2, stats.mean.data_ptr(), stats.var.data_ptr(),
-                                 stats.rstd.data_ptr(), base, err.data_ptr(), SEAM_MAX_SPINS, _stamps_ptr(), _stream()), "mcl_dense_block_fwd")
+    call("mcl_dense_block_fwd", px, B, H, W, Ct, C0, L, arr, eps1, eps2, stats.mean,
+         stats.var, stats.rstd, base, err, SEAM_MAX_SPINS, BLOCK_STAMPS)
     return zs
 
 
@@ -1315,11 +1258,9 @@ def conv0_fwd(x: Tensor, w16: Tensor, eps: float, stats: Optional[Tuple[Tensor, 
     rstd) tensors of 64 floats, or None) the batch statistics of y for norm0 from the kernel's epilogue."""
     B, _, H, W = x.shape
     y = torch.empty((B, 64, H // 2, W // 2), device=x.device, dtype=torch.bfloat16, memory_format=CL)
-    L = _lib.lib()
-    ws = _ws(L.mcl_conv0_workspace_floats(B, H, W), x.device)
-    st = (None, None, None) if stats is None else tuple(t.data_ptr() for t in stats)
-    check(L.mcl_conv0_fwd(x.data_ptr(), B, H, W, w16.data_ptr(), y.data_ptr(), ws.data_ptr(), eps, *st, _stream()),
-          "mcl_conv0_fwd")
+    ws = _ws(call("mcl_conv0_workspace_floats", B, H, W), x.device)
+    st = (None, None, None) if stats is None else stats
+    call("mcl_conv0_fwd", x, B, H, W, w16, y, ws, eps, *st)
     return y
 
 
@@ -1349,11 +1290,9 @@ class Conv0Fn(torch.autograd.Function):
             ctx.cap["dy"] = dy
         B, _, H, W = x.shape
         if _direct_all(w) and dy.dtype == torch.bfloat16:
-            L = _lib.lib()
-            ws = _ws(L.mcl_conv0_wrw_workspace_floats(B, H, W), x.device)
+            ws = _ws(call("mcl_conv0_wrw_workspace_floats", B, H, W), x.device)
             tgt, in_place = _grad_target_khwc(w)
-            check(L.mcl_conv0_wrw(x.data_ptr(), B, H, W, dy.data_ptr(), ws.data_ptr(), tgt.data_ptr(), int(in_place),
-                                  _stream()), "mcl_conv0_wrw")                          # straight into the fp32 .grad
+            call("mcl_conv0_wrw", x, B, H, W, dy, ws, tgt, in_place)                          # straight into the fp32 .grad
             _grad_finish_khwc(w, tgt, in_place)
             return None, None, None
         from . import conv_generic as cg
@@ -1376,7 +1315,7 @@ class AvgPool2Fn(torch.autograd.Function):
     def forward(ctx, x):
         B, C, H, W = x.shape
         y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=x.dtype, memory_format=CL)
-        check(_lib.lib().mcl_avgpool2_nhwc_bf16(x.data_ptr(), y.data_ptr(), B, H, W, C, 0, _stream()), "mcl_avgpool2")
+        call("mcl_avgpool2_nhwc_bf16", x, y, B, H, W, C, 0)
         ctx.shape = (B, C, H, W)
         return y
 
@@ -1385,7 +1324,7 @@ class AvgPool2Fn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         dy = dense_cl(dy)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=dy.dtype, memory_format=CL)
-        check(_lib.lib().mcl_avgpool2_nhwc_bf16(dy.data_ptr(), dx.data_ptr(), B, H, W, C, 1, _stream()), "mcl_avgpool2")
+        call("mcl_avgpool2_nhwc_bf16", dy, dx, B, H, W, C, 1)
         return dx
 
 
@@ -1397,8 +1336,7 @@ class MaxPool3s2Fn(torch.autograd.Function):
         B, C, H, W = x.shape
         y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=x.dtype, memory_format=CL)
         idx = torch.empty((B, y.shape[2], y.shape[3], C), device=x.device, dtype=torch.uint8)
-        check(_lib.lib().mcl_maxpool3s2_nhwc_bf16_fwd(x.data_ptr(), y.data_ptr(), idx.data_ptr(), B, H, W, C, _stream()),
-              "mcl_maxpool")
+        call("mcl_maxpool3s2_nhwc_bf16_fwd", x, y, idx, B, H, W, C)
         ctx.save_for_backward(idx)
         ctx.shape = (B, C, H, W)
         return y
@@ -1409,8 +1347,7 @@ class MaxPool3s2Fn(torch.autograd.Function):
         B, C, H, W = ctx.shape
         dy = dense_cl(dy)
         dx = torch.empty((B, C, H, W), device=dy.device, dtype=dy.dtype, memory_format=CL)
-        check(_lib.lib().mcl_maxpool3s2_nhwc_bf16_bwd(idx.data_ptr(), dy.data_ptr(), dx.data_ptr(), B, H, W, C, _stream()),
-              "mcl_maxpool bwd")
+        call("mcl_maxpool3s2_nhwc_bf16_bwd", idx, dy, dx, B, H, W, C)
         return dx
 
 
@@ -1423,9 +1360,7 @@ class StemTailFn(torch.autograd.Function):
         B, C, H, W = x.shape
         y = torch.empty((B, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), device=x.device, dtype=x.dtype, memory_format=CL)
         idx = torch.empty((B, y.shape[2], y.shape[3], C), device=x.device, dtype=torch.uint8)
-        check(_lib.lib().mcl_bn_act_maxpool_fwd(x.data_ptr(), B, H, W, C, gamma.data_ptr(), beta.data_ptr(),
-                                                mean.data_ptr(), rstd.data_ptr(), y.data_ptr(), idx.data_ptr(),
-                                                _stream()), "mcl_bn_act_maxpool_fwd")
+        call("mcl_bn_act_maxpool_fwd", x, B, H, W, C, gamma, beta, mean, rstd, y, idx)
         ctx.save_for_backward(x, idx, mean, rstd)
         ctx.params = (gamma, beta)
         ctx.cap = None
@@ -1445,8 +1380,7 @@ class StemTailFn(torch.autograd.Function):
         if ctx.cap is not None:
             ctx.cap["dy"] = dy.clone(memory_format=CL)
         g = torch.empty_like(x, memory_format=CL)           # un-pooled gradient (gather, deterministic)
-        check(_lib.lib().mcl_maxpool3s2_nhwc_bf16_bwd_ld(idx.data_ptr(), pdy, lddy, g.data_ptr(), B, H, W, C, _stream()),
-              "mcl_maxpool bwd")
+        call("mcl_maxpool3s2_nhwc_bf16_bwd_ld", idx, pdy, lddy, g, B, H, W, C)
         direct = _direct_all(gamma, beta)
         dg, db = bn_act_bwd(g, x, gamma, beta, mean, rstd, True, g, False, into_param_grads=direct)   # dx in place of g
         if ctx.cap is not None:
@@ -1495,8 +1429,7 @@ def bn_act_avgpool_fwd(x: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, rst
     B, C, H, W = x.shape
     px, S, _, ld = _rows(x)
     p = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=x.dtype, memory_format=CL)
-    check(_lib.lib().mcl_bn_act_avgpool_fwd(px, ld, B, H, W, C, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-                                            rstd.data_ptr(), p.data_ptr(), C, _stream()), "mcl_bn_act_avgpool_fwd")
+    call("mcl_bn_act_avgpool_fwd", px, ld, B, H, W, C, gamma, beta, mean, rstd, p, C)
     return p
 
 
@@ -1512,13 +1445,11 @@ def pooled_conv1x1_fwd(p: Tensor, w16: Tensor, eps: float, stats: Optional[_Bloc
     one, zero = _identity_bn(p.device)
     pp, S, _, ldp = _rows(p)
     assert (Sy, Cy) == (S, Co) and y.dtype == p.dtype
-    L = _lib.lib()
-    ws = _ws(L.mcl_dense_conv1x1_workspace_floats(S), p.device)
+    ws = _ws(call("mcl_dense_conv1x1_workspace_floats", S), p.device)
     for n0 in range(0, Co, 128):
         st = (None, None, None) if stats is None else tuple(t.data_ptr() + 4 * n0 for t in (stats.mean, stats.var, stats.rstd))
-        check(L.mcl_dense_conv1x1_fwd(pp, ldp, S, C, one.data_ptr(), zero.data_ptr(), zero.data_ptr(), one.data_ptr(),
-                                      w16.data_ptr() + 2 * n0 * C, py + 2 * n0, ldy, ws.data_ptr(), eps,
-                                      *st, _stream()), "mcl_dense_conv1x1_fwd (transition)")
+        call("mcl_dense_conv1x1_fwd", pp, ldp, S, C, one, zero, zero, one,
+             w16.data_ptr() + 2 * n0 * C, py + 2 * n0, ldy, ws, eps, *st)
     return y
 
 
@@ -1568,9 +1499,8 @@ class TransitionFn(torch.autograd.Function):
         pdy, Sq, Co_, lddy = _rows(dy)
         assert Co_ == Co and dy.dtype == torch.bfloat16
         dp = torch.empty((B, C, dy.shape[2], dy.shape[3]), device=buf.device, dtype=torch.bfloat16, memory_format=CL)
-        check(_lib.lib().mcl_gemm_bf16(pdy, lddy, 0, w16.data_ptr(), C, 0, dp.data_ptr(), C, 0, Sq, C, Co, 1, 1, 0, 0, 0,
-                                       1.0, 2, None, None, 0, 0, None, 0, None, 0, 1, None, 0, _stream()),
-              "mcl_gemm_bf16 (transition backward-data)")
+        call("mcl_gemm_bf16", pdy, lddy, 0, w16, C, 0, dp, C, 0, Sq, C, Co, 1,
+             1, 0, 0, 0, 1.0, 2, None, None, 0, 0, None, 0, None, 0, 1, None, 0)
         dx = torch.empty_like(buf, memory_format=CL)
         direct = _direct_all(gamma, beta)
         if direct:
@@ -1578,12 +1508,8 @@ class TransitionFn(torch.autograd.Function):
         else:
             dg = torch.empty(C, device=buf.device, dtype=torch.float32)
             db = torch.empty(C, device=buf.device, dtype=torch.float32)
-        L = _lib.lib()
-        ws = _ws(L.mcl_bn_workspace_floats(B * H * W, C, 1), buf.device)
-        check(L.mcl_bn_act_avgpool_bwd(dp.data_ptr(), C, buf.data_ptr(), C, B, H, W, C, gamma.data_ptr(),
-                                       beta.data_ptr(), stats.mean.data_ptr(), stats.rstd.data_ptr(), ws.data_ptr(),
-                                       dg.data_ptr(), db.data_ptr(), int(direct), dx.data_ptr(), C, _stream()),
-              "mcl_bn_act_avgpool_bwd")
+        ws = _ws(call("mcl_bn_workspace_floats", B * H * W, C, 1), buf.device)
+        call("mcl_bn_act_avgpool_bwd", dp, C, buf, C, B, H, W, C, gamma, beta, stats.mean, stats.rstd, ws, dg, db, direct, dx, C)
         # dW += dy^T p, straight into w.grad when it exists (it needs only dy and p): on the side stream -- behind the deferred
         # weight gradients of the dense block before, joined by the dense block that follows in the backward order -- or here
         dw = _side_fork(buf.device, lambda: conv1x1_wrw(dy, p, w), (dy, p), lanes=lanes, event=ev)
@@ -1605,8 +1531,7 @@ class BNGlobalPoolFn(torch.autograd.Function):
         px, S, _, ld = _rows(x)
         out = torch.empty((B, C), device=x.device, dtype=torch.float32)
         xm = torch.empty((B, C), device=x.device, dtype=torch.float32)
-        check(_lib.lib().mcl_bn_gap_fwd(px, ld, B, H * W, C, gamma.data_ptr(), beta.data_ptr(), mean.data_ptr(),
-                                        rstd.data_ptr(), out.data_ptr(), xm.data_ptr(), _stream()), "mcl_bn_gap_fwd")
+        call("mcl_bn_gap_fwd", px, ld, B, H * W, C, gamma, beta, mean, rstd, out, xm)
         ctx.save_for_backward(x, xm, mean, rstd)
         ctx.params = (gamma, beta)
         ctx.cap = None
@@ -1632,9 +1557,7 @@ class BNGlobalPoolFn(torch.autograd.Function):
             dg = torch.empty(C, device=x.device, dtype=torch.float32)
             db = torch.empty(C, device=x.device, dtype=torch.float32)
         coef = torch.empty(2 * C, device=x.device, dtype=torch.float32)
-        check(_lib.lib().mcl_bn_gap_bwd(g.data_ptr(), xm.data_ptr(), px, ld, B, H * W, C, gamma.data_ptr(), mean.data_ptr(),
-                                        rstd.data_ptr(), coef.data_ptr(), dg.data_ptr(), db.data_ptr(), int(direct),
-                                        dx.data_ptr(), C, _stream()), "mcl_bn_gap_bwd")
+        call("mcl_bn_gap_bwd", g, xm, px, ld, B, H * W, C, gamma, mean, rstd, coef, dg, db, direct, dx, C)
         if ctx.cap is not None:
             ctx.cap.update({"g": g, "dx": dx.clone(memory_format=CL)})     # (dx becomes block 4's gradient buffer, in place)
         return dx, (None if direct else dg), (None if direct else db), None, None
@@ -1658,8 +1581,7 @@ def image_to_act(x: Tensor, act_dtype: torch.dtype, out: Optional[Tensor] = None
         else:
             y = torch.empty((B, C, H, W), device=x.device, dtype=torch.bfloat16, memory_format=CL)
         sb, sc, sy, sx = x.stride()
-        check(_lib.lib().mcl_image_to_bf16_nhwc(x.data_ptr(), sb, sc, sy, sx, B, C, H, W, y.data_ptr(), _stream()),
-              "mcl_image_to_bf16_nhwc")
+        call("mcl_image_to_bf16_nhwc", x, sb, sc, sy, sx, B, C, H, W, y)
         return y
     y = x.to(dtype=act_dtype).contiguous(memory_format=CL)
     if out is not None:
@@ -1794,9 +1716,8 @@ def eval_rstd(bns) -> List[Tensor]:
             raise RuntimeError("eval_rstd: running statistics must be contiguous fp32")
     n = len(bns)
     vp = C.c_void_p * n
-    check(_lib.lib().mcl_bn_eval_rstd(n, vp(*[bn.running_var.data_ptr() for bn in bns]), vp(*[t.data_ptr() for t in outs]),
-                                      (C.c_int32 * n)(*sizes), (C.c_float * n)(*[float(bn.eps) for bn in bns]), _stream()),
-          "mcl_bn_eval_rstd")
+    call("mcl_bn_eval_rstd", n, vp(*[bn.running_var.data_ptr() for bn in bns]), vp(*[t.data_ptr() for t in outs]),
+         (C.c_int32 * n)(*sizes), (C.c_float * n)(*[float(bn.eps) for bn in bns]))
     return outs
 
 
@@ -1889,9 +1810,7 @@ def densenet_features_eval(features: nn.Sequential, x: Tensor, act_dtype: torch.
             bn = features.norm5
             B, C, H, W = buf.shape
             out = torch.empty((B, C), device=buf.device, dtype=torch.float32)
-            check(_lib.lib().mcl_bn_gap_fwd(buf.data_ptr(), C, B, H * W, C, bn.weight.data_ptr(), bn.bias.data_ptr(),
-                                            bn.running_mean.data_ptr(), rs[id(bn)].data_ptr(), out.data_ptr(), None,
-                                            _stream()), "mcl_bn_gap_fwd")
+            call("mcl_bn_gap_fwd", buf, C, B, H * W, C, bn.weight, bn.bias, bn.running_mean, rs[id(bn)], out, None)
         else:
             out = affine(buf, features.norm5, False)
             if pooled:

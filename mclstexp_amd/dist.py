@@ -170,27 +170,23 @@ class HipPrims:
 
     @staticmethod
     def row_lse(S: Tensor) -> Tensor:
-        from . import _lib, ops
+        from ._lib import call
         out = torch.empty((S.shape[0],), device=S.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mcl_infonce_lse(S.data_ptr(), S.stride(0), S.shape[0], S.shape[1], out.data_ptr(), None,
-                                              ops._stream()), "mcl_infonce_lse")
+        call("mcl_infonce_lse", S, S.stride(0), S.shape[0], S.shape[1], out, None)
         return out
 
     @staticmethod
     def col_lse(S: Tensor) -> Tensor:
-        from . import _lib, ops
+        from ._lib import call
         out = torch.empty((S.shape[1],), device=S.device, dtype=torch.float32)
-        _lib.check(_lib.lib().mcl_infonce_lse(S.data_ptr(), S.stride(0), S.shape[0], S.shape[1], None, out.data_ptr(),
-                                              ops._stream()), "mcl_infonce_lse")
+        call("mcl_infonce_lse", S, S.stride(0), S.shape[0], S.shape[1], None, out)
         return out
 
     @staticmethod
     def dlogits(S: Tensor, row_lse: Tensor, col_lse: Tensor, row0: int, col0: int, coef: float) -> Tensor:
-        from . import _lib, ops
+        from ._lib import call
         dS = torch.empty_like(S)
-        _lib.check(_lib.lib().mcl_infonce_dlogits(S.data_ptr(), S.stride(0), row_lse.data_ptr(), col_lse.data_ptr(),
-                                                  S.shape[0], S.shape[1], row0, col0, coef, dS.data_ptr(),
-                                                  dS.stride(0), ops._stream()), "mcl_infonce_dlogits")
+        call("mcl_infonce_dlogits", S, S.stride(0), row_lse, col_lse, S.shape[0], S.shape[1], row0, col0, coef, dS, dS.stride(0))
         return dS
 
     @staticmethod

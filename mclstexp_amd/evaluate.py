@@ -26,10 +26,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _arrays, _lib, ops
+from . import _arrays
 from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, device, empty, load_gene_major, paired_offsets, stack_rows, upload,
                       write_json)
-from ._lib import check
+from ._lib import call
 
 # dataset -> (top_k, ord of the distance norm in the weighting)
 PRESETS = {"her2st": (200, 1), "cscc": (600, 2), "10x": (200, 2)}
@@ -63,10 +63,8 @@ def metrics_device(pred: Tensor, true: Tensor, offsets: Sequence[int], n_heg: in
     r, true_mean, summary = e((S, G), torch.float64), e((S, G), torch.float64), e((S, 5), torch.float64)
     heg = e((S, n_heg), torch.int64)
     work = e((2 * S * G,), torch.float64)
-    check(_lib.lib().mcl_expr_metrics(pred.data_ptr(), pred.stride(0), FLOAT_CODE[pred.dtype], true.data_ptr(),
-                                      true.stride(0), FLOAT_CODE[true.dtype], off_d.data_ptr(), S, G, n_heg,
-                                      r.data_ptr(), true_mean.data_ptr(), heg.data_ptr(), summary.data_ptr(),
-                                      work.data_ptr(), ops._stream()), "mcl_expr_metrics")
+    call("mcl_expr_metrics", pred, pred.stride(0), FLOAT_CODE[pred.dtype], true, true.stride(0),
+         FLOAT_CODE[true.dtype], off_d, S, G, n_heg, r, true_mean, heg, summary, work)
     return {"r": r, "true_mean": true_mean, "heg": heg, "summary": summary}
 
 

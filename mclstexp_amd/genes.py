@@ -24,9 +24,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, evaluate, ops
+from . import evaluate
 from ._arrays import ArrayLike, Tensor, device, empty, load_gene_major, matrix, paired_offsets, upload
-from ._lib import check
+from ._lib import call
 
 TOP_N = 7
 PRED_FILE = evaluate.PRED_FILE     # what the tutorial reads per slide; ``evaluate --save_pred`` writes it
@@ -58,8 +58,7 @@ def pvalues_device(r: Tensor, offsets: Sequence[int]) -> Tuple[Tensor, Tensor]:
         off_d = upload(evaluate.validate_offsets(off, off[-1]), r.device)
     e = empty(r.device)
     p, nl = e((S, G), torch.float64), e((S, G), torch.float64)
-    check(_lib.lib().mcl_pearson_pvalue(r.data_ptr(), off_d.data_ptr(), S, G, p.data_ptr(), nl.data_ptr(),
-                                        ops._stream()), "mcl_pearson_pvalue")
+    call("mcl_pearson_pvalue", r, off_d, S, G, p, nl)
     return p, nl
 
 
@@ -110,9 +109,7 @@ def rank_genes(neglog10p: ArrayLike, r: ArrayLike, top_n: int = TOP_N, log_space
     e = empty(dev)
     mean, best_value, best_r = e((G,), torch.float64), e((G,), torch.float64), e((G,), torch.float64)
     n_defined, best_slide, order = e((G,), torch.int32), e((G,), torch.int32), e((G,), torch.int64)
-    check(_lib.lib().mcl_gene_rank(nl.data_ptr(), rr.data_ptr(), S, G, top_n, mean.data_ptr(), n_defined.data_ptr(),
-                                   order.data_ptr(), best_slide.data_ptr(), best_value.data_ptr(), best_r.data_ptr(),
-                                   ops._stream()), "mcl_gene_rank")
+    call("mcl_gene_rank", nl, rr, S, G, top_n, mean, n_defined, order, best_slide, best_value, best_r)
     mean_h, order_h = mean.cpu().numpy(), order.cpu().numpy()
     slide_h, value_h, r_h = best_slide.cpu().numpy(), best_value.cpu().numpy(), best_r.cpu().numpy()
     top = [{"gene": int(g), "mean": float(mean_h[g]), "best_slide": int(slide_h[g]), "best_value": float(value_h[g]),

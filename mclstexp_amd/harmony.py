@@ -40,7 +40,7 @@ import torch
 
 from . import _lib
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, device, empty, load_gene_major, matrix, upload
-from ._lib import check
+from ._lib import call
 
 MAX_K, MAX_B = 128, 31
 LLOYD_ITERS = 25                       # harmonypy's max_iter of its k-means initialisation
@@ -56,10 +56,6 @@ class HarmonyResult:
     objective_harmony: List[float]
     kmeans_rounds: List[int]
     converged: bool
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------------- host rules
@@ -150,68 +146,53 @@ class _Device:
 
     def __init__(self, N: int, K: int, d: int, B: int, dev: torch.device):
         self.N, self.K, self.d, self.B, self.dev = N, K, d, B, dev
-        self.lib = _lib.lib()
+        self.lib = _lib.lib()            # (tests/test_harmony_gpu.py calls single entry points through it)
         e = empty(dev)
         f8 = torch.float64
-        self.work = e((max(int(self.lib.mcl_harmony_workspace_doubles(N, K, d, B)), 8),), f8)
+        self.work = e((max(int(call("mcl_harmony_workspace_doubles", N, K, d, B)), 8),), f8)
         self.D, self.S, self.R = e((N, K), f8), e((N, K), f8), e((N, K), f8)
         self.Y = e((K, d), f8)
         self.E, self.O = e((K, B), f8), e((K, B), f8)
         self.obj = e((3,), f8)
 
     def normalize(self, z: Tensor, by_max: bool, z64: Optional[Tensor], zc: Tensor) -> None:
-        check(self.lib.mcl_harmony_normalize(z.data_ptr(), z.stride(0), FLOAT_CODE[z.dtype], self.N, self.d, int(by_max),
-                                             None if z64 is None else z64.data_ptr(), zc.data_ptr(), _stream()),
-              "mcl_harmony_normalize")
+        call("mcl_harmony_normalize", z, z.stride(0), FLOAT_CODE[z.dtype], self.N, self.d, by_max, z64, zc)
 
     def centroids(self, zc: Tensor) -> None:
-        check(self.lib.mcl_harmony_centroids(self.R.data_ptr(), zc.data_ptr(), None, self.N, self.K, self.d, 0, 1,
-                                             self.work.data_ptr(), self.Y.data_ptr(), _stream()), "mcl_harmony_centroids")
+        call("mcl_harmony_centroids", self.R, zc, None, self.N, self.K, self.d, 0, 1, self.work, self.Y)
 
     def moe_sums(self, z: Tensor, batch: Tensor, out: Tensor) -> None:
-        check(self.lib.mcl_harmony_centroids(self.R.data_ptr(), z.data_ptr(), batch.data_ptr(), self.N, self.K, self.d,
-                                             self.B, 0, self.work.data_ptr(), out.data_ptr(), _stream()),
-              "mcl_harmony_centroids")
+        call("mcl_harmony_centroids", self.R, z, batch, self.N, self.K, self.d, self.B, 0, self.work, out)
 
     def dist(self, zc: Tensor) -> None:
-        check(self.lib.mcl_harmony_dist(zc.data_ptr(), self.Y.data_ptr(), self.N, self.K, self.d, 0, self.D.data_ptr(),
-                                        _stream()), "mcl_harmony_dist")
+        call("mcl_harmony_dist", zc, self.Y, self.N, self.K, self.d, 0, self.D)
 
     def softmax(self, sigma: float, normalize: bool, out: Tensor) -> None:
-        check(self.lib.mcl_harmony_softmax(self.D.data_ptr(), self.N, self.K, sigma, int(normalize), out.data_ptr(),
-                                           _stream()), "mcl_harmony_softmax")
+        call("mcl_harmony_softmax", self.D, self.N, self.K, sigma, normalize, out)
 
     def moments(self, batch: Tensor, pr: Tensor) -> None:
-        check(self.lib.mcl_harmony_moments(self.R.data_ptr(), batch.data_ptr(), self.N, self.K, self.B, pr.data_ptr(),
-                                           self.E.data_ptr(), self.O.data_ptr(), _stream()), "mcl_harmony_moments")
+        call("mcl_harmony_moments", self.R, batch, self.N, self.K, self.B, pr, self.E, self.O)
 
     def update_blocks(self, batch: Tensor, order: Tensor, nb: int, theta: Tensor, pr: Tensor) -> None:
-        check(self.lib.mcl_harmony_update_block(self.R.data_ptr(), self.S.data_ptr(), batch.data_ptr(), order.data_ptr(),
-                                                self.N, self.K, self.B, nb, 0, nb, theta.data_ptr(), pr.data_ptr(),
-                                                self.E.data_ptr(), self.O.data_ptr(), _stream()),
-              "mcl_harmony_update_block")
+        call("mcl_harmony_update_block", self.R, self.S, batch, order,
+             self.N, self.K, self.B, nb, 0, nb, theta, pr, self.E, self.O)
 
     def objective(self, batch: Tensor, theta: Tensor, sigma: float) -> float:
-        check(self.lib.mcl_harmony_objective(self.R.data_ptr(), self.D.data_ptr(), batch.data_ptr(), self.E.data_ptr(),
-                                             self.O.data_ptr(), theta.data_ptr(), self.N, self.K, self.B, sigma,
-                                             self.work.data_ptr(), self.obj.data_ptr(), _stream()), "mcl_harmony_objective")
+        call("mcl_harmony_objective", self.R, self.D, batch, self.E, self.O,
+             theta, self.N, self.K, self.B, sigma, self.work, self.obj)
         t = self.obj.cpu().numpy()                      # the one synchronisation per k-means iteration
         return float(t[0] + t[1] + t[2])
 
     def ridge(self, M: Tensor, lamb: Tensor, W: Tensor) -> None:
-        check(self.lib.mcl_harmony_ridge(self.O.data_ptr(), M.data_ptr(), lamb.data_ptr(), self.K, self.B, self.d,
-                                         W.data_ptr(), _stream()), "mcl_harmony_ridge")
+        call("mcl_harmony_ridge", self.O, M, lamb, self.K, self.B, self.d, W)
 
     def apply(self, z: Tensor, W: Tensor, batch: Tensor, out: Tensor) -> None:
-        check(self.lib.mcl_harmony_apply(z.data_ptr(), self.R.data_ptr(), W.data_ptr(), batch.data_ptr(), self.N, self.K,
-                                         self.B, self.d, out.data_ptr(), _stream()), "mcl_harmony_apply")
+        call("mcl_harmony_apply", z, self.R, W, batch, self.N, self.K, self.B, self.d, out)
 
     def lloyd(self, zc: Tensor, seeds: Tensor) -> None:
         e = empty(self.dev)
         labels, sums = e((self.N,), torch.int32), e((self.K, self.d), torch.float64)
-        check(self.lib.mcl_harmony_lloyd(zc.data_ptr(), self.N, self.K, self.d, seeds.data_ptr(), LLOYD_ITERS,
-                                         labels.data_ptr(), self.D.data_ptr(), sums.data_ptr(), self.work.data_ptr(),
-                                         self.Y.data_ptr(), _stream()), "mcl_harmony_lloyd")
+        call("mcl_harmony_lloyd", zc, self.N, self.K, self.d, seeds, LLOYD_ITERS, labels, self.D, sums, self.work, self.Y)
 
 
 def run_harmony(data: ArrayLike, batch: Sequence, *, theta: Union[float, Sequence[float]] = 2.0,
@@ -273,8 +254,7 @@ def run_harmony(data: ArrayLike, batch: Sequence, *, theta: Union[float, Sequenc
     # 1. initialisation
     if init_centroids is not None:
         y0 = matrix(init_centroids, "init_centroids", dev, (torch.float64,), torch.float64, dense=True)
-        check(g.lib.mcl_harmony_normalize(y0.data_ptr(), d, 1, K, d, 0, None, g.Y.data_ptr(), _stream()),
-              "mcl_harmony_normalize")
+        call("mcl_harmony_normalize", y0, d, 1, K, d, 0, None, g.Y)
     else:
         rows = np.asarray(seed_rows) if seed_rows is not None else rng.choice(N, K, replace=False)
         g.lloyd(zc, upload(rows.astype(np.int32), dev))

@@ -18,8 +18,8 @@ from typing import Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _lib, ops
-from ._lib import check
+from . import ops
+from ._lib import call
 
 Tensor = torch.Tensor
 ArrayLike = Union[np.ndarray, Tensor]
@@ -68,8 +68,7 @@ def extract_patches(whole_image: Tensor, centers_rc: ArrayLike, r: int = 112, hf
         out16 = torch.empty((n, p, p, 3), device=img.device, dtype=torch.bfloat16)
     else:
         raise ValueError("layout must be 'nchw_f32' or 'nhwc_bf16'")
-    check(_lib.lib().mcl_patch_gather(img.data_ptr(), img.shape[0], img.shape[1], c.data_ptr(), n, r, ops._p(opb),
-                                      float(divisor), ops._p(out32), ops._p(out16), ops._stream()), "mcl_patch_gather")
+    call("mcl_patch_gather", img, img.shape[0], img.shape[1], c, n, r, opb, float(divisor), out32, out16)
     return out32 if out32 is not None else out16.permute(0, 3, 1, 2)
 
 
@@ -96,9 +95,7 @@ def log_library_size_normalize(counts: ArrayLike, rescale: float = 1e4) -> Tenso
     x = torch.as_tensor(np.asarray(counts, dtype=np.float32)) if not isinstance(counts, Tensor) else counts
     x = ops._rowmajor(x.to(_dev(), dtype=torch.float32), "counts")
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    check(_lib.lib().mcl_log_library_size_normalize(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), x.shape[0],
-                                                    x.shape[1], float(rescale), ops._stream()),
-          "mcl_log_library_size_normalize")
+    call("mcl_log_library_size_normalize", x, x.stride(0), y, y.stride(0), x.shape[0], x.shape[1], float(rescale))
     return y
 
 
@@ -178,7 +175,5 @@ def her2st_train_patches(whole_image: Tensor, centers_xy: ArrayLike, r: int = 11
         out16 = torch.empty((n, p, p, 3), device=img.device, dtype=torch.bfloat16)
     else:
         raise ValueError("layout must be 'nchw_f32' or 'nhwc_bf16'")
-    check(_lib.lib().mcl_her2st_train_patches(img.data_ptr(), img.shape[0], img.shape[1], c.data_ptr(), n, r,
-                                              prm.data_ptr(), 255.0, ops._p(out32), ops._p(out16), ops._stream()),
-          "mcl_her2st_train_patches")
+    call("mcl_her2st_train_patches", img, img.shape[0], img.shape[1], c, n, r, prm, 255.0, out32, out16)
     return out32 if out32 is not None else out16.permute(0, 3, 1, 2)

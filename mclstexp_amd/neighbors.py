@@ -31,10 +31,10 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _arrays, _lib, cluster
+from . import _arrays, cluster
 from . import preprocess as _pre       # expression_graph has an argument of the module's name
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload
-from ._lib import check
+from ._lib import call
 
 MAX_DIM = 64             # csrc/neighbors.hip
 MAX_ROWS = 16384         # per segment: one row of distances lives in LDS
@@ -44,10 +44,6 @@ N_NEIGHBORS = 150        # BLEEP_inference.ipynb visualize_umap_clusters
 N_PCS = 50
 N_TOP_GENES = 1024
 OUT_FILE = "neighbors.npz"
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------------- host rules
@@ -104,33 +100,27 @@ class _Plan:
         self.off, self.seg, self.k, self.dev = off, seg, int(k), dev
         self.S, self.rows = int(seg.size), int(off[-1])
         self.min_n, self.max_n = int(seg.min()), int(seg.max())
-        self.lib = _lib.lib()
         self.off_d = upload(off, dev)
-        self.work = empty(dev)((max(int(self.lib.mcl_knn_workspace_bytes(self.rows, self.k)), 8) // 8 + 1,), torch.float64)
+        self.work = empty(dev)((max(int(call("mcl_knn_workspace_bytes", self.rows, self.k)), 8) // 8 + 1,), torch.float64)
 
     def _sizes(self):
         return self.S, self.rows, self.min_n, self.max_n, self.k
 
     def knn(self, xd: Tensor, idx: Tensor, dist: Tensor) -> None:
-        check(self.lib.mcl_knn_exact(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], int(xd.shape[1]),
-                                     self.off_d.data_ptr(), *self._sizes(), idx.data_ptr(), dist.data_ptr(), _stream()),
-              "mcl_knn_exact")
+        call("mcl_knn_exact", xd, xd.stride(0), FLOAT_CODE[xd.dtype], int(xd.shape[1]), self.off_d, *self._sizes(), idx, dist)
 
     def smooth(self, dist: Tensor, rho: Tensor, sigma: Tensor) -> None:
-        check(self.lib.mcl_knn_smooth(dist.data_ptr(), self.off_d.data_ptr(), *self._sizes(), self.work.data_ptr(),
-                                      rho.data_ptr(), sigma.data_ptr(), _stream()), "mcl_knn_smooth")
+        call("mcl_knn_smooth", dist, self.off_d, *self._sizes(), self.work, rho, sigma)
 
     def connectivities(self, idx: Tensor, dist: Tensor, rho: Tensor, sigma: Tensor, mix: float):
         """(indptr, indices, data, nnz_offsets): the count, the one read of S integers, the fill."""
         e = empty(self.dev)
         indptr, nnz = e((self.rows + self.S,), torch.int64), e((self.S,), torch.int64)
 
-        def call(phase, nnz_off, total, indices, data):
-            check(self.lib.mcl_knn_connectivities(idx.data_ptr(), dist.data_ptr(), rho.data_ptr(), sigma.data_ptr(),
-                                                  self.off_d.data_ptr(), *self._sizes(), float(mix), phase,
-                                                  self.work.data_ptr(), indptr.data_ptr(), nnz.data_ptr(), nnz_off, total,
-                                                  indices, data, _stream()), "mcl_knn_connectivities")
-        call(0, None, 0, None, None)
+        def phase(which, nnz_off, total, indices, data):
+            call("mcl_knn_connectivities", idx, dist, rho, sigma, self.off_d, *self._sizes(),
+                 float(mix), which, self.work, indptr, nnz, nnz_off, total, indices, data)
+        phase(0, None, 0, None, None)
         counts = nnz.cpu().numpy()                     # the one synchronisation
         if (counts < 0).any():
             raise RuntimeError("mcl_knn_connectivities skipped a segment: the offsets on the device do not match the host's")
@@ -138,7 +128,7 @@ class _Plan:
         total = int(nnz_off[-1])
         indices, data = e((max(total, 1),), torch.int32), e((max(total, 1),), torch.float64)
         nnz_off_d = upload(nnz_off, self.dev)
-        call(1, nnz_off_d.data_ptr(), total, indices.data_ptr(), data.data_ptr())
+        phase(1, nnz_off_d, total, indices, data)
         return indptr, indices[:total], data[:total], nnz_off
 
 

@@ -15,7 +15,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import (COMPUTE_BF16, COMPUTE_F32, EPI_ACCUM, EPI_GELU, EPI_GELU_BWD, GemmArgs, check)
+from ._lib import (COMPUTE_BF16, COMPUTE_F32, EPI_ACCUM, EPI_GELU, EPI_GELU_BWD, GemmArgs, call)
 
 Tensor = torch.Tensor
 LN_EPS = 1e-5
@@ -52,8 +52,7 @@ class forced_compute:
         return False
 
 
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
+_stream = _lib.current_stream            # (tests and tools that call the C ABI directly pass it)
 
 
 def _chk(t: Tensor, name: str = "tensor") -> Tensor:
@@ -109,11 +108,11 @@ def gemm_raw(M: int, N: int, K: int, batch: int, A: Tensor, sAm: int, sAk: int, 
     a.pre_out, a.ldp = _p(pre_out), ldp
     a.aux, a.ldaux = _p(aux), ldaux
     a.compute = _compute_mode if compute is None else compute
-    ks = _lib.lib().mcl_gemm_auto_ksplit(M, N, K, batch) if (SPLIT_K and filt is None) else 1
+    ks = call("mcl_gemm_auto_ksplit", M, N, K, batch) if (SPLIT_K and filt is None) else 1
     if ks > 1:    # skinny problem (M = a batch of spots): K slices + fixed-order merge fill the chip
         ws = torch.empty(ks * batch * M * N, device=Cmat.device, dtype=torch.float32)
         a.ksplit, a.workspace = ks, ws.data_ptr()
-    check(_lib.lib().mcl_gemm(C.byref(a), _stream()), "mcl_gemm")
+    call("mcl_gemm", C.byref(a))
 
 
 def linear_fwd(x: Tensor, W: Tensor, bias: Optional[Tensor] = None, gelu: bool = False,
@@ -187,12 +186,10 @@ def colsum(x: Tensor, param: Optional[Tensor] = None) -> Optional[Tensor]:
     x = _rowmajor(x, "x")
     ws = _rowred_ws(x.shape[0], x.shape[1], x.device)
     if param is not None and param.shape == (x.shape[1],) and _direct_grad_ok(param):
-        check(_lib.lib().mcl_colsum_ws(x.data_ptr(), x.stride(0), param.grad.data_ptr(), x.shape[0], x.shape[1], 1, _p(ws),
-                                       _stream()), "mcl_colsum")
+        call("mcl_colsum_ws", x, x.stride(0), param.grad, x.shape[0], x.shape[1], 1, ws)
         return None
     out = torch.empty((x.shape[1],), device=x.device, dtype=torch.float32)
-    check(_lib.lib().mcl_colsum_ws(x.data_ptr(), x.stride(0), out.data_ptr(), x.shape[0], x.shape[1], 0, _p(ws), _stream()),
-          "mcl_colsum")
+    call("mcl_colsum_ws", x, x.stride(0), out, x.shape[0], x.shape[1], 0, ws)
     return out
 
 
@@ -211,7 +208,7 @@ def colred_group(sums, norms=()):
         t = q.grad if direct else torch.empty((x.shape[1],), device=x.device, dtype=torch.float32)
         out_s.append(None if direct else t)
         a.append(x.data_ptr()); lda.append(x.stride(0)); xs.append(None); ldx.append(0); mean.append(None); rstd.append(None)
-        o0.append(t.data_ptr()); o1.append(None); cols.append(x.shape[1]); acc.append(int(direct))
+        o0.append(t.data_ptr()); o1.append(None); cols.append(x.shape[1]); acc.append(direct)
     for dy, x, mu, rs, params in norms:
         dy, x = _rowmajor(dy, "dy"), _rowmajor(x, "x")
         rows = x.shape[0] if rows is None else rows
@@ -227,11 +224,11 @@ def colred_group(sums, norms=()):
         out_n.append((None, None) if direct else (dg, db))
         a.append(dy.data_ptr()); lda.append(dy.stride(0)); xs.append(x.data_ptr()); ldx.append(x.stride(0))
         mean.append(mu.data_ptr()); rstd.append(rs.data_ptr())
-        o0.append(dg.data_ptr()); o1.append(db.data_ptr()); cols.append(n); acc.append(int(direct))
+        o0.append(dg.data_ptr()); o1.append(db.data_ptr()); cols.append(n); acc.append(direct)
     n = len(a)
     vp, i64, i32 = C.c_void_p * n, C.c_int64 * n, C.c_int32 * n
-    check(_lib.lib().mcl_colred_group(n, vp(*a), i64(*lda), vp(*xs), i64(*ldx), vp(*mean), vp(*rstd), vp(*o0), vp(*o1), i32(*cols),
-                                      i32(*acc), rows, _stream()), "mcl_colred_group")
+    call("mcl_colred_group", n, vp(*a), i64(*lda), vp(*xs), i64(*ldx),
+         vp(*mean), vp(*rstd), vp(*o0), vp(*o1), i32(*cols), i32(*acc), rows)
     return out_s, out_n
 
 
@@ -239,7 +236,7 @@ def _rowred_ws(rows: int, cols: int, device) -> Optional[Tensor]:
     """Chunk-partial workspace of the many-row column reductions (None for the spot branch's few rows: the one-launch forms)."""
     if rows <= 1024:
         return None
-    return torch.empty(_lib.lib().mcl_rowred_workspace_floats(rows, cols), device=device, dtype=torch.float32)
+    return torch.empty(call("mcl_rowred_workspace_floats", rows, cols), device=device, dtype=torch.float32)
 
 
 # --------------------------------------------------------------------------- LayerNorm
@@ -249,9 +246,7 @@ def layernorm_fwd(x: Tensor, gamma: Tensor, beta: Tensor, eps: float = LN_EPS) -
     y = torch.empty((rows, cols), device=x.device, dtype=torch.float32)
     mean = torch.empty((rows,), device=x.device, dtype=torch.float32)
     rstd = torch.empty((rows,), device=x.device, dtype=torch.float32)
-    check(_lib.lib().mcl_layernorm_fwd(x.data_ptr(), x.stride(0), _chk(gamma).data_ptr(), _chk(beta).data_ptr(),
-                                       y.data_ptr(), cols, mean.data_ptr(), rstd.data_ptr(), rows, cols, eps,
-                                       _stream()), "mcl_layernorm_fwd")
+    call("mcl_layernorm_fwd", x, x.stride(0), _chk(gamma), _chk(beta), y, cols, mean, rstd, rows, cols, eps)
     return y, mean, rstd
 
 
@@ -266,10 +261,8 @@ def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tens
     if dx_only:
         if dx_add is not None:
             dx_add = _rowmajor(dx_add, "dx_add")
-        check(_lib.lib().mcl_layernorm_bwd_ws(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gamma.data_ptr(),
-                                              mean.data_ptr(), rstd.data_ptr(), _p(dx_add),
-                                              dx_add.stride(0) if dx_add is not None else 0, dx.data_ptr(), cols, None, None, 0,
-                                              rows, cols, None, _stream()), "mcl_layernorm_bwd")
+        call("mcl_layernorm_bwd_ws", dy, dy.stride(0), x, x.stride(0), gamma, mean, rstd, dx_add,
+             dx_add.stride(0) if dx_add is not None else 0, dx, cols, None, None, 0, rows, cols, None)
         return dx, None, None
     direct = (params is not None and params[0].shape == (cols,) and params[1].shape == (cols,)
               and _direct_grad_ok(params[0]) and _direct_grad_ok(params[1]))
@@ -280,11 +273,8 @@ def layernorm_bwd(dy: Tensor, x: Tensor, gamma: Tensor, mean: Tensor, rstd: Tens
         db = torch.empty((cols,), device=x.device, dtype=torch.float32)
     if dx_add is not None:
         dx_add = _rowmajor(dx_add, "dx_add")
-    check(_lib.lib().mcl_layernorm_bwd_ws(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), gamma.data_ptr(),
-                                          mean.data_ptr(), rstd.data_ptr(), _p(dx_add),
-                                          dx_add.stride(0) if dx_add is not None else 0, dx.data_ptr(), cols,
-                                          dg.data_ptr(), db.data_ptr(), int(direct), rows, cols,
-                                          _p(_rowred_ws(rows, cols, x.device)), _stream()), "mcl_layernorm_bwd")
+    call("mcl_layernorm_bwd_ws", dy, dy.stride(0), x, x.stride(0), gamma, mean, rstd, dx_add,
+         dx_add.stride(0) if dx_add is not None else 0, dx, cols, dg, db, direct, rows, cols, _rowred_ws(rows, cols, x.device))
     return (dx, None, None) if direct else (dx, dg, db)
 
 
@@ -327,8 +317,7 @@ def attention_core_fwd(qkv: Tensor, heads: int, dim_head: int, nseq: int = 1) ->
         T = rows // nseq
         out = torch.empty((rows, inner), device=qkv.device, dtype=torch.float32)
         lse = torch.empty((nseq * heads, T), device=qkv.device, dtype=torch.float32)
-        check(_lib.lib().mcl_attention_batched_fwd(qkv.data_ptr(), qkv.stride(0), T, nseq, heads, dim_head, dim_head ** -0.5,
-                                                   out.data_ptr(), inner, lse.data_ptr(), _stream()), "mcl_attention_batched_fwd")
+        call("mcl_attention_batched_fwd", qkv, qkv.stride(0), T, nseq, heads, dim_head, dim_head ** -0.5, out, inner, lse)
         return out, lse
     if nseq != 1:
         raise RuntimeError("attention: several sequences need the fused kernel (head dimension 64, fp32, aligned rows)")
@@ -347,9 +336,8 @@ def attention_core_bwd(dout: Tensor, qkv: Tensor, out: Tensor, aux: Tensor, head
         out = out.contiguous()
     dqkv = torch.empty((rows, 3 * inner), device=qkv.device, dtype=torch.float32)
     dvec = torch.empty((nseq * heads, T), device=qkv.device, dtype=torch.float32)
-    check(_lib.lib().mcl_attention_batched_bwd(qkv.data_ptr(), qkv.stride(0), T, nseq, heads, dim_head, dim_head ** -0.5,
-                                               out.data_ptr(), dout.data_ptr(), inner, aux.data_ptr(), dvec.data_ptr(),
-                                               dqkv.data_ptr(), 3 * inner, _stream()), "mcl_attention_batched_bwd")
+    call("mcl_attention_batched_bwd", qkv, qkv.stride(0), T, nseq, heads,
+         dim_head, dim_head ** -0.5, out, dout, inner, aux, dvec, dqkv, 3 * inner)
     return dqkv
 
 
@@ -361,8 +349,7 @@ def attention_core_fwd_unfused(qkv: Tensor, heads: int, dim_head: int) -> Tuple[
     P = torch.empty((heads, B, B), device=qkv.device, dtype=torch.float32)
     # scores_h = q_h k_h^T
     gemm_raw(B, B, dim_head, heads, qkv, ld, 1, dim_head, qkv, 1, ld, dim_head, P, B, B * B, b_off=inner)
-    check(_lib.lib().mcl_softmax_rows_fwd(P.data_ptr(), B, heads * B, B, dim_head ** -0.5, _stream()),
-          "mcl_softmax_rows_fwd")
+    call("mcl_softmax_rows_fwd", P, B, heads * B, B, dim_head ** -0.5)
     out = torch.empty((B, inner), device=qkv.device, dtype=torch.float32)
     # out_h = P_h v_h
     gemm_raw(B, dim_head, B, heads, P, B, 1, B * B, qkv, ld, 1, dim_head, out, inner, dim_head, b_off=2 * inner)
@@ -383,8 +370,7 @@ def attention_core_bwd_unfused(dout: Tensor, qkv: Tensor, P: Tensor, heads: int,
     # dP_h = dO_h v_h^T
     dP = torch.empty_like(P)
     gemm_raw(B, B, dim_head, heads, dout, ldo, 1, dim_head, qkv, 1, ld, dim_head, dP, B, B * B, b_off=2 * inner)
-    check(_lib.lib().mcl_softmax_rows_bwd(P.data_ptr(), dP.data_ptr(), B, heads * B, B, dim_head ** -0.5, _stream()),
-          "mcl_softmax_rows_bwd")
+    call("mcl_softmax_rows_bwd", P, dP, B, heads * B, B, dim_head ** -0.5)
     # dq_h = dS_h k_h ; dk_h = dS_h^T q_h
     gemm_raw(B, dim_head, B, heads, dP, B, 1, B * B, qkv, ld, 1, dim_head, dqkv, ldq, dim_head, b_off=inner)
     gemm_raw(B, dim_head, B, heads, dP, 1, B, B * B, qkv, ld, 1, dim_head, dqkv, ldq, dim_head, c_off=inner)
@@ -432,7 +418,7 @@ class AttnBlockFn(torch.autograd.Function):
         q_bo, q_b1, q_b2, q_g1, q_be1, q_g2, q_be2, q_bqkv = ctx.bparams
         rows = x.shape[0]
         if (GROUP_LAYER_GRADS and _mode_of(ctx.compute) == COMPUTE_F32 and rows <= 1024
-                and all(_lib.lib().mcl_gemm_auto_ksplit(w.shape[0], w.shape[1], rows, 1) == 1 for w in (wqkv, wo, w1, w2))):
+                and all(call("mcl_gemm_auto_ksplit", w.shape[0], w.shape[1], rows, 1) == 1 for w in (wqkv, wo, w1, w2))):
             # The spot branch (rows = one batch of spots): the data-gradient chain first, then the four weight gradients as ONE
             # grouped launch and the bias + LayerNorm parameter gradients as another -- 2 launches where they were 9 (K = rows <=
             # 255: none of them is a split-K problem; each result is bit-identical to its separate launch).
@@ -522,7 +508,7 @@ def _head_counter_words(owner: Tensor, n: int) -> Tensor:
     t = _head_counters.get(key)
     if t is None or t.numel() < n:
         t = torch.empty(max(n, 1024), device=owner.device, dtype=torch.int32)
-        check(_lib.lib().mcl_fill_zero(t.data_ptr(), t.numel() * 4, _stream()), "mcl_fill_zero")
+        call("mcl_fill_zero", t, t.numel() * 4)
         _head_counters[key] = t
     return t
 
@@ -537,7 +523,7 @@ def gemm_group(problems) -> None:
         a.batch, a.alpha, a.compute = 1, 1.0, _lib.COMPUTE_F32
         for k, v in kw.items():
             setattr(a, k, v)
-    check(_lib.lib().mcl_gemm_group(arr, n, _stream()), "mcl_gemm_group")
+    call("mcl_gemm_group", arr, n)
 
 
 def _fused_head_ok(x: Tensor, wp: Tensor, wf: Tensor, vecs=()) -> bool:
@@ -554,14 +540,11 @@ def proj_head_fwd(x: Tensor, wp: Tensor, bp: Tensor, wf: Tensor, bf: Tensor, g: 
     e, p, a, z = (torch.empty((M, HEAD_P), device=dev, dtype=torch.float32) for _ in range(4))
     mean = torch.empty((M,), device=dev, dtype=torch.float32)
     rstd = torch.empty((M,), device=dev, dtype=torch.float32)
-    L = _lib.lib()
-    ks = int(os.environ.get("MCL_HEAD_KSPLIT", "0")) or L.mcl_proj_head_ksplit(M, D)
-    ws = torch.empty(L.mcl_proj_head_ws_floats(M, ks), device=dev, dtype=torch.float32)
+    ks = int(os.environ.get("MCL_HEAD_KSPLIT", "0")) or call("mcl_proj_head_ksplit", M, D)
+    ws = torch.empty(call("mcl_proj_head_ws_floats", M, ks), device=dev, dtype=torch.float32)
     cnt = _head_counter_words(wp, (M + 15) // 16 + 1)
-    check(L.mcl_proj_head_fwd(x.data_ptr(), x.stride(0), M, D, wp.data_ptr(), wp.stride(0), bp.data_ptr(), wf.data_ptr(),
-                              wf.stride(0), bf.data_ptr(), g.data_ptr(), be.data_ptr(), eps, e.data_ptr(), p.data_ptr(),
-                              a.data_ptr(), z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), ws.data_ptr(), cnt.data_ptr(), ks,
-                              _stream()), "mcl_proj_head_fwd")
+    call("mcl_proj_head_fwd", x, x.stride(0), M, D, wp, wp.stride(0), bp, wf,
+         wf.stride(0), bf, g, be, eps, e, p, a, z, mean, rstd, ws, cnt, ks)
     return e, p, a, z, mean, rstd
 
 
@@ -586,10 +569,8 @@ def proj_head_bwd_rows(de: Tensor, z: Tensor, mean: Tensor, rstd: Tensor, g: Ten
     nrb = (M + 15) // 16
     ws = torch.empty(nrb * 4 * HEAD_P, device=dev, dtype=torch.float32)
     cnt = _head_counter_words(wf, nrb + 1)
-    check(_lib.lib().mcl_proj_head_bwd_rows(de.data_ptr(), de.stride(0), M, z.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                                            g.data_ptr(), p.data_ptr(), wf.data_ptr(), wf.stride(0), dz.data_ptr(), dp.data_ptr(),
-                                            ptrs[0], ptrs[1], ptrs[2], ptrs[3], mask, ws.data_ptr(),
-                                            cnt.data_ptr() + 4 * nrb, _stream()), "mcl_proj_head_bwd_rows")
+    call("mcl_proj_head_bwd_rows", de, de.stride(0), M, z, mean, rstd, g, p, wf, wf.stride(0),
+         dz, dp, ptrs[0], ptrs[1], ptrs[2], ptrs[3], mask, ws, cnt.data_ptr() + 4 * nrb)
     return dz, dp, outs
 
 
@@ -664,9 +645,7 @@ class RowSparseGrad:
     def to_dense(self, n_rows: int) -> Tensor:
         G = self.rows.shape[1]
         dense = torch.zeros((n_rows, G), device=self.rows.device, dtype=torch.float32)
-        check(_lib.lib().mcl_embed_scatter_rows(self.owner_idx.data_ptr(), self.rows.data_ptr(), self.rows.stride(0),
-                                                dense.data_ptr(), G, self.rows.shape[0], G, 0, _stream()),
-              "mcl_embed_scatter_rows")
+        call("mcl_embed_scatter_rows", self.owner_idx, self.rows, self.rows.stride(0), dense, G, self.rows.shape[0], G, 0)
         return dense
 
 
@@ -675,8 +654,7 @@ def embed_rowgrad(d_out: Tensor, idx: Tensor) -> RowSparseGrad:
     B, G = d_out.shape
     owner = torch.empty((B,), device=d_out.device, dtype=torch.int32)
     rows = torch.empty((B, G), device=d_out.device, dtype=torch.float32)
-    check(_lib.lib().mcl_embed_rowgrad(d_out.data_ptr(), d_out.stride(0), idx.data_ptr(), owner.data_ptr(),
-                                       rows.data_ptr(), G, B, G, _stream()), "mcl_embed_rowgrad")
+    call("mcl_embed_rowgrad", d_out, d_out.stride(0), idx, owner, rows, G, B, G)
     return RowSparseGrad(owner, rows)
 
 
@@ -761,10 +739,8 @@ class PosEmbedAddFn(torch.autograd.Function):
         out = torch.empty((B, G), device=expr.device, dtype=torch.float32)
         ix = torch.empty((B,), device=expr.device, dtype=torch.int32)
         iy = torch.empty((B,), device=expr.device, dtype=torch.int32)
-        check(_lib.lib().mcl_pos_embed_add_fwd(expr.data_ptr(), expr.stride(0), pos.data_ptr(), xt.data_ptr(),
-                                               yt.data_ptr(), G, xt.shape[0], out.data_ptr(), G, ix.data_ptr(),
-                                               iy.data_ptr(), position_error_flag(expr.device).data_ptr(), B, G,
-                                               _stream()), "mcl_pos_embed_add_fwd")
+        call("mcl_pos_embed_add_fwd", expr, expr.stride(0), pos, xt, yt, G,
+             xt.shape[0], out, G, ix, iy, position_error_flag(expr.device), B, G)
         ctx.save_for_backward(ix, iy)
         ctx.n_rows = xt.shape[0]
         ctx.sink = sparse_sink
@@ -798,20 +774,17 @@ def infonce_fwd_bwd(e_spot: Tensor, e_img: Tensor, temperature: float, want_logi
     B, P = es.shape
     assert ei.shape == (B, P)
     dev = es.device
-    L = _lib.lib()
     S = torch.empty((B, B), device=dev, dtype=torch.float32)
     gemm_raw(B, B, P, 1, es, es.stride(0), 1, 0, ei, 1, ei.stride(0), 0, S, B, 0, alpha=1.0 / temperature)
     lse = torch.empty((2, B), device=dev, dtype=torch.float32)
-    check(L.mcl_infonce_lse(S.data_ptr(), B, B, B, lse[0].data_ptr(), lse[1].data_ptr(), _stream()), "mcl_infonce_lse")
+    call("mcl_infonce_lse", S, B, B, B, lse[0], lse[1])
     loss = torch.empty((), device=dev, dtype=torch.float32)
-    check(L.mcl_infonce_loss_mean(S.data_ptr(), B, lse[0].data_ptr(), lse[1].data_ptr(), B, 2.0 * B, loss.data_ptr(),
-                                  _stream()), "mcl_infonce_loss_mean")
+    call("mcl_infonce_loss_mean", S, B, lse[0], lse[1], B, 2.0 * B, loss)
     dS = torch.empty_like(S)
-    check(L.mcl_infonce_dlogits(S.data_ptr(), B, lse[0].data_ptr(), lse[1].data_ptr(), B, B, 0, 0,
-                                1.0 / (2.0 * B * temperature), dS.data_ptr(), B, _stream()), "mcl_infonce_dlogits")
+    call("mcl_infonce_dlogits", S, B, lse[0], lse[1], B, B, 0, 0, 1.0 / (2.0 * B * temperature), dS, B)
     d_es = torch.empty_like(es)
     d_ei = torch.empty_like(ei)
-    if _compute_mode == COMPUTE_F32 and (not SPLIT_K or L.mcl_gemm_auto_ksplit(B, P, B, 1) == 1):
+    if _compute_mode == COMPUTE_F32 and (not SPLIT_K or call("mcl_gemm_auto_ksplit", B, P, B, 1) == 1):
         # both gradient products as one launch (on the step's critical chain between loss and backward); bit-identical
         gemm_group([dict(M=B, N=P, K=B, A=dS.data_ptr(), sAm=B, sAk=1, B=ei.data_ptr(), sBk=ei.stride(0), sBn=1,
                          C=d_es.data_ptr(), ldc=P),                                # dE_s = dS E_i
@@ -829,9 +802,7 @@ _fused_ws = {}
 
 
 def _fused_workspace(R: int, C: int, device) -> Tensor:
-    need = _lib.lib().mcl_infonce_fused_workspace_bytes(R, C, FUSED_DIM)
-    if need < 0:
-        raise RuntimeError(f"mcl_infonce_fused_workspace_bytes rejected R={R} C={C}")
+    need = call("mcl_infonce_fused_workspace_bytes", R, C, FUSED_DIM)
     key = (device.index, torch.cuda.current_stream().cuda_stream)
     w = _fused_ws.get(key)
     if w is None or w.numel() < need:
@@ -844,8 +815,7 @@ def cast_bf16(x: Tensor) -> Tensor:
     """fp32 (rows, cols) -> contiguous bf16 copy (round to nearest even) on the HIP cast kernel."""
     x = _rowmajor(x, "x")
     y = torch.empty(x.shape, device=x.device, dtype=torch.bfloat16)
-    check(_lib.lib().mcl_cast_f32_to_bf16(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), x.shape[0],
-                                          x.shape[1], _stream()), "mcl_cast_f32_to_bf16")
+    call("mcl_cast_f32_to_bf16", x, x.stride(0), y, y.stride(0), x.shape[0], x.shape[1])
     return y
 
 
@@ -867,9 +837,8 @@ def infonce_fused_lse(a16: Tensor, b16: Tensor, inv_t: float, diag_off: int = 0)
     lse = torch.empty((R,), device=a16.device, dtype=torch.float32)
     diag = torch.zeros((R,), device=a16.device, dtype=torch.float32)
     ws = _fused_workspace(R, Cn, a16.device)
-    check(_lib.lib().mcl_infonce_fused_lse(a16.data_ptr(), a16.stride(0), b16.data_ptr(), b16.stride(0), R, Cn, FUSED_DIM, diag_off, inv_t,
-                                           lse.data_ptr(), diag.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
-          "mcl_infonce_fused_lse")
+    call("mcl_infonce_fused_lse", a16, a16.stride(0), b16, b16.stride(0),
+         R, Cn, FUSED_DIM, diag_off, inv_t, lse, diag, ws, ws.numel())
     return lse, diag
 
 
@@ -881,9 +850,8 @@ def infonce_fused_grad(a16: Tensor, b16: Tensor, inv_t: float, lse_a: Tensor, ls
     assert lse_a.shape == (R,) and lse_b.shape == (Cn,) and lse_a.is_contiguous() and lse_b.is_contiguous()
     dA = torch.empty((R, FUSED_DIM), device=a16.device, dtype=torch.float32)
     ws = _fused_workspace(R, Cn, a16.device)
-    check(_lib.lib().mcl_infonce_fused_grad(a16.data_ptr(), a16.stride(0), b16.data_ptr(), b16.stride(0), R, Cn, FUSED_DIM, diag_off, inv_t,
-                                            _chk(lse_a).data_ptr(), _chk(lse_b).data_ptr(), coef, dA.data_ptr(),
-                                            ws.data_ptr(), ws.numel(), _stream()), "mcl_infonce_fused_grad")
+    call("mcl_infonce_fused_grad", a16, a16.stride(0), b16, b16.stride(0), R, Cn,
+         FUSED_DIM, diag_off, inv_t, _chk(lse_a), _chk(lse_b), coef, dA, ws, ws.numel())
     return dA
 
 
@@ -926,9 +894,8 @@ def quant_e4m3(x: Tensor, want_deq: bool = True) -> Tuple[Tensor, Optional[Tenso
         raise RuntimeError(f"the fp8 InfoNCE kernels are built for projection_dim {FUSED_DIM}, got {cols}")
     packed = torch.zeros((rows, FP8_ROW), device=x.device, dtype=torch.uint8)
     deq = torch.empty((rows, cols), device=x.device, dtype=torch.bfloat16) if want_deq else None
-    check(_lib.lib().mcl_quant_e4m3_rows(x.data_ptr(), x.stride(0), rows, cols, packed.data_ptr(), FP8_ROW,
-                                         packed.data_ptr() + FUSED_DIM, FP8_ROW, _p(deq), cols if want_deq else 0,
-                                         _stream()), "mcl_quant_e4m3_rows")
+    call("mcl_quant_e4m3_rows", x, x.stride(0), rows, cols, packed, FP8_ROW,
+         packed.data_ptr() + FUSED_DIM, FP8_ROW, deq, cols if want_deq else 0)
     return packed, deq
 
 
@@ -943,9 +910,8 @@ def dequant_e4m3(packed: Tensor) -> Tensor:
     packed = _fp8_rows(packed, "packed")
     rows = packed.shape[0]
     deq = torch.empty((rows, FUSED_DIM), device=packed.device, dtype=torch.bfloat16)
-    check(_lib.lib().mcl_dequant_e4m3_rows(packed.data_ptr(), packed.stride(0), packed.data_ptr() + FUSED_DIM,
-                                           packed.stride(0), rows, FUSED_DIM, deq.data_ptr(), FUSED_DIM, _stream()),
-          "mcl_dequant_e4m3_rows")
+    call("mcl_dequant_e4m3_rows", packed, packed.stride(0), packed.data_ptr() + FUSED_DIM,
+         packed.stride(0), rows, FUSED_DIM, deq, FUSED_DIM)
     return deq
 
 
@@ -953,15 +919,13 @@ def infonce_fp8_lse(a8: Tensor, b8: Tensor, inv_t: float) -> Tensor:
     """lse (R,) of S = dequant(a8) dequant(b8)^T * inv_t on the fp8 MFMA (hardware block scales), S never in HBM."""
     a8, b8 = _fp8_rows(a8, "a8"), _fp8_rows(b8, "b8")
     R, Cn = a8.shape[0], b8.shape[0]
-    L = _lib.lib()
-    need = L.mcl_infonce_fp8_workspace_bytes(R, Cn)
+    need = call("mcl_infonce_fp8_workspace_bytes", R, Cn)
     ws = _fused_workspace(R, Cn, a8.device)
     if ws.numel() < need:
         ws = torch.empty(int(need), device=a8.device, dtype=torch.uint8)
     lse = torch.empty((R,), device=a8.device, dtype=torch.float32)
-    check(L.mcl_infonce_fp8_lse(a8.data_ptr(), a8.stride(0), a8.data_ptr() + FUSED_DIM, a8.stride(0), b8.data_ptr(),
-                                b8.stride(0), b8.data_ptr() + FUSED_DIM, b8.stride(0), R, Cn, FUSED_DIM, inv_t,
-                                lse.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "mcl_infonce_fp8_lse")
+    call("mcl_infonce_fp8_lse", a8, a8.stride(0), a8.data_ptr() + FUSED_DIM, a8.stride(0), b8, b8.stride(0),
+         b8.data_ptr() + FUSED_DIM, b8.stride(0), R, Cn, FUSED_DIM, inv_t, lse, ws, ws.numel())
     return lse
 
 
@@ -969,8 +933,7 @@ def infonce_rowdot(a16: Tensor, b16: Tensor, inv_t: float, diag_off: int = 0) ->
     a16, b16 = _bf16_rows(a16, "a"), _bf16_rows(b16, "b")
     R, Cn = a16.shape[0], b16.shape[0]
     diag = torch.zeros((R,), device=a16.device, dtype=torch.float32)
-    check(_lib.lib().mcl_infonce_rowdot_bf16(a16.data_ptr(), a16.stride(0), b16.data_ptr(), b16.stride(0), R, Cn, FUSED_DIM,
-                                             diag_off, inv_t, diag.data_ptr(), _stream()), "mcl_infonce_rowdot_bf16")
+    call("mcl_infonce_rowdot_bf16", a16, a16.stride(0), b16, b16.stride(0), R, Cn, FUSED_DIM, diag_off, inv_t, diag)
     return diag
 
 
@@ -1037,8 +1000,7 @@ class DropoutFn(torch.autograd.Function):
         mask = torch.empty(x.shape, device=x.device, dtype=torch.uint8)
         _dropout_calls += 1
         seed = (torch.initial_seed() * 0x9E3779B1 + _dropout_calls) & 0xFFFFFFFFFFFFFFFF
-        check(_lib.lib().mcl_dropout_fwd(x.data_ptr(), y.data_ptr(), mask.data_ptr(), x.numel(), float(p), seed, _stream()),
-              "mcl_dropout_fwd")
+        call("mcl_dropout_fwd", x, y, mask, x.numel(), float(p), seed)
         ctx.save_for_backward(mask)
         ctx.p = float(p)
         return y
@@ -1048,8 +1010,7 @@ class DropoutFn(torch.autograd.Function):
         (mask,) = ctx.saved_tensors
         dy = dy.contiguous()
         dx = torch.empty_like(dy)
-        check(_lib.lib().mcl_dropout_bwd(dy.data_ptr(), mask.data_ptr(), dx.data_ptr(), dy.numel(), ctx.p, _stream()),
-              "mcl_dropout_bwd")
+        call("mcl_dropout_bwd", dy, mask, dx, dy.numel(), ctx.p)
         return dx, None
 
 
@@ -1057,7 +1018,7 @@ def gelu_bwd(dy: Tensor, pre: Tensor) -> Tensor:
     """dy * gelu'(pre) (exact erf form) in one own launch."""
     dy, pre = dy.contiguous(), pre.contiguous()
     out = torch.empty_like(dy)
-    check(_lib.lib().mcl_gelu_f32(pre.data_ptr(), dy.data_ptr(), out.data_ptr(), dy.numel(), _stream()), "mcl_gelu_f32")
+    call("mcl_gelu_f32", pre, dy, out, dy.numel())
     return out
 
 
@@ -1066,7 +1027,7 @@ class GeluFn(torch.autograd.Function):
     def forward(ctx, x):
         x = _chk(x, "gelu input").contiguous()
         y = torch.empty_like(x)
-        check(_lib.lib().mcl_gelu_f32(x.data_ptr(), None, y.data_ptr(), x.numel(), _stream()), "mcl_gelu_f32")
+        call("mcl_gelu_f32", x, None, y, x.numel())
         ctx.save_for_backward(x)
         return y
 
@@ -1084,7 +1045,7 @@ class AddFn(torch.autograd.Function):
         a, b = _chk(a, "a").contiguous(), _chk(b, "b").contiguous()
         assert a.shape == b.shape
         y = torch.empty_like(a)
-        check(_lib.lib().mcl_add_f32(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), _stream()), "mcl_add_f32")
+        call("mcl_add_f32", a, b, y, a.numel())
         return y
 
     @staticmethod
@@ -1107,7 +1068,6 @@ def soft_clip_fwd_bwd(e_spot: Tensor, e_img: Tensor, temperature: float, targets
     B, P = es.shape
     assert ei.shape == (B, P)
     dev = es.device
-    L = _lib.lib()
     inv_t = 1.0 / temperature
     k = temperature if targets_times_temperature else inv_t
     S = torch.empty((B, B), device=dev, dtype=torch.float32)
@@ -1116,22 +1076,21 @@ def soft_clip_fwd_bwd(e_spot: Tensor, e_img: Tensor, temperature: float, targets
     gemm_raw(B, B, P, 1, ei, ei.stride(0), 1, 0, ei, 1, ei.stride(0), 0, Tg, B, 0, alpha=0.5, compute=COMPUTE_F32)
     gemm_raw(B, B, P, 1, es, es.stride(0), 1, 0, es, 1, es.stride(0), 0, Tg, B, 0, alpha=0.5, flags=EPI_ACCUM,
              compute=COMPUTE_F32)
-    check(L.mcl_softmax_rows_fwd(Tg.data_ptr(), B, B, B, k, _stream()), "mcl_softmax_rows_fwd")      # Tg in place
+    call("mcl_softmax_rows_fwd", Tg, B, B, B, k)      # Tg in place
     lse = torch.empty((2, B), device=dev, dtype=torch.float32)
-    check(L.mcl_infonce_lse(S.data_ptr(), B, B, B, lse[0].data_ptr(), lse[1].data_ptr(), _stream()), "mcl_infonce_lse")
+    call("mcl_infonce_lse", S, B, B, B, lse[0], lse[1])
     c = 1.0 / (2.0 * B)
     # the elementwise middle in one pass (csrc/soft_clip.hip): loss partials, dS, d loss / d Tg
     tcol = colsum(Tg)
     dS = torch.empty((B, B), device=dev, dtype=torch.float32)
     dA = torch.empty((B, B), device=dev, dtype=torch.float32)
     loss_rows = torch.empty((B, 1), device=dev, dtype=torch.float32)
-    check(L.mcl_soft_clip_mid(S.data_ptr(), Tg.data_ptr(), lse[0].data_ptr(), lse[1].data_ptr(), tcol.data_ptr(), B, c,
-                              dS.data_ptr(), dA.data_ptr(), loss_rows.data_ptr(), _stream()), "mcl_soft_clip_mid")
+    call("mcl_soft_clip_mid", S, Tg, lse[0], lse[1], tcol, B, c, dS, dA, loss_rows)
     loss = colsum(loss_rows)[0]
     # backward through the soft targets
-    check(L.mcl_softmax_rows_bwd(Tg.data_ptr(), dA.data_ptr(), B, B, B, k, _stream()), "mcl_softmax_rows_bwd")
+    call("mcl_softmax_rows_bwd", Tg, dA, B, B, B, k)
     dsym = torch.empty((B, B), device=dev, dtype=torch.float32)  # A = (II + SS)/2 and both Gram matrices are symmetric
-    check(L.mcl_symmetrize(dA.data_ptr(), B, dsym.data_ptr(), _stream()), "mcl_symmetrize")
+    call("mcl_symmetrize", dA, B, dsym)
     d_es = torch.empty_like(es)
     d_ei = torch.empty_like(ei)
     gemm_raw(B, P, B, 1, dS, B, 1, 0, ei, ei.stride(0), 1, 0, d_es, P, 0, alpha=inv_t, compute=COMPUTE_F32)
@@ -1149,8 +1108,7 @@ def scale_pair(d_es: Tensor, d_ei: Tensor, gl: Tensor) -> Tuple[Tensor, Tensor]:
     gl = gl.reshape(1).to(torch.float32)            # (no launch for the fp32 scalar autograd hands over)
     d_es, d_ei = d_es.contiguous(), d_ei.contiguous()
     ya, yb = torch.empty_like(d_es), torch.empty_like(d_ei)
-    check(_lib.lib().mcl_scale2_f32(d_es.data_ptr(), d_es.numel(), d_ei.data_ptr(), d_ei.numel(), gl.data_ptr(),
-                                    ya.data_ptr(), yb.data_ptr(), _stream()), "mcl_scale2_f32")
+    call("mcl_scale2_f32", d_es, d_es.numel(), d_ei, d_ei.numel(), gl, ya, yb)
     return ya, yb
 
 

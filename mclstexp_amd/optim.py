@@ -27,8 +27,8 @@ from typing import Callable, Dict, List, Optional
 
 import torch
 
-from . import _lib, ops
-from ._lib import check
+from . import ops
+from ._lib import call
 
 Tensor = torch.Tensor
 
@@ -247,7 +247,7 @@ class FusedAdam(torch.optim.Optimizer):
         for f in self._flat.values():
             if f.get("n", 0) > 0:
                 if f["g"].is_cuda:      # own fill kernel (the captured step graph holds kernel nodes only)
-                    check(_lib.lib().mcl_fill_zero(f["g"].data_ptr(), 4 * f["g"].numel(), ops._stream()), "mcl_fill_zero")
+                    call("mcl_fill_zero", f["g"], 4 * f["g"].numel())
                 else:
                     f["g"].zero_()
                 flat_ids.update(id(p) for p in f["params"])
@@ -275,8 +275,6 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
-        st = ops._stream()
         lazy = self._lazy_active()
         tables_pending = self._sink is not None and (self._sink.get("tables_done", False) or "dout" in self._sink)
         skipped_tables = lazy and not tables_pending and any(self.state.get(t["param"]) for t in self._tables.values())
@@ -292,7 +290,7 @@ class FusedAdam(torch.optim.Optimizer):
             self._lazy_flushed_at = self._step_count + 1
         tables_done = self._sink is not None and self._sink.pop("tables_done", False)
         if lazy and tables_pending and not tables_done:
-            self._tables_step_lazy(L, st)
+            self._tables_step_lazy()
             tables_done = True
         deferred = []
         for gi, group in enumerate(self.param_groups):
@@ -308,7 +306,7 @@ class FusedAdam(torch.optim.Optimizer):
                 tab = self._tables.get(id(p))
                 if tab is not None and self._sink is not None and (tables_done or "dout" in self._sink):
                     if not tables_done:
-                        self._table_step(L, st, p, tab, gi)
+                        self._table_step(p, tab, gi)
                     continue
                 if p.grad is None:
                     continue                        # torch.optim.Adam skips parameters without a gradient
@@ -319,9 +317,8 @@ class FusedAdam(torch.optim.Optimizer):
                 g = p.grad
                 if g.stride() != p.stride():
                     g = torch.empty_like(p).copy_(g)   # same memory order as p (the update is elementwise)
-                check(L.mcl_adam_step_dev(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(),
-                                          state["exp_avg_sq"].data_ptr(), p.numel(),
-                                          self._dev_state(gi, p.device)["consts"].data_ptr(), st), "mcl_adam_step_dev")
+                call("mcl_adam_step_dev", p, g, state["exp_avg"], state["exp_avg_sq"],
+                     p.numel(), self._dev_state(gi, p.device)["consts"])
         for h in (wait or []):
             h.wait()
         fused_shadow = []
@@ -329,14 +326,11 @@ class FusedAdam(torch.optim.Optimizer):
             sh = f.get("shadow_" + str(torch.bfloat16))
             if sh is not None:
                 # the update also writes the bf16 shadow the backbone kernels read: no cast pass after the step
-                check(L.mcl_adam_step_dev_shadow(f["p"].data_ptr(), f["g"].data_ptr(), f["m"].data_ptr(), f["v"].data_ptr(),
-                                                 f["n"], self._dev_state(gi, f["p"].device)["consts"].data_ptr(),
-                                                 sh.data_ptr(), st), "mcl_adam_step_dev_shadow")
+                call("mcl_adam_step_dev_shadow", f["p"], f["g"], f["m"], f["v"],
+                     f["n"], self._dev_state(gi, f["p"].device)["consts"], sh)
                 fused_shadow.append(gi)
                 continue
-            check(L.mcl_adam_step_dev(f["p"].data_ptr(), f["g"].data_ptr(), f["m"].data_ptr(), f["v"].data_ptr(),
-                                      f["n"], self._dev_state(gi, f["p"].device)["consts"].data_ptr(), st),
-                  "mcl_adam_step_dev")
+            call("mcl_adam_step_dev", f["p"], f["g"], f["m"], f["v"], f["n"], self._dev_state(gi, f["p"].device)["consts"])
         if self._sink is not None:
             if self._sink.get("static"):
                 # graph-captured backward: dout/ix/iy are static buffers refreshed by every replay
@@ -411,15 +405,12 @@ class FusedAdam(torch.optim.Optimizer):
         self.sync_hyper()
         self._flush_if_due()
         self._lazy_dirty = True
-        L = _lib.lib()
-        st = ops._stream()
         for gi, group in enumerate(self.param_groups):
             dev = next((p.device for p in group["params"] if p.is_cuda), None)
             if dev is None:
                 continue
             d = self._dev_state(gi, dev)
-            check(L.mcl_adam_consts_update_hist(d["step"].data_ptr(), d["consts"].data_ptr(), d["hyper"].data_ptr(),
-                                                d["hist"].data_ptr(), HIST_LEN, st), "mcl_adam_consts_update_hist")
+            call("mcl_adam_consts_update_hist", d["step"], d["consts"], d["hyper"], d["hist"], HIST_LEN)
 
     def pre_replay(self) -> None:
         """Host-side work that must precede the replay of a captured step (engine.TrainStep): hyper-parameter upload and,
@@ -432,15 +423,13 @@ class FusedAdam(torch.optim.Optimizer):
         """Called by ops.PosEmbedAddFn.backward once sink['dout'|'ix'|'iy'] exist (single process)."""
         if self._sink is None or "dout" not in self._sink:
             return
-        L = _lib.lib()
-        st = ops._stream()
         self._begin_step()
         if self._lazy_active():
-            self._tables_step_lazy(L, st)
+            self._tables_step_lazy()
         else:
             for tab in self._tables.values():
                 p = tab["param"]
-                self._table_step(L, st, p, tab, self._group_of[id(p)])
+                self._table_step(p, tab, self._group_of[id(p)])
         self._sink["tables_done"] = True
 
     # ------------------------------------------------------------------ lazy-exact tables
@@ -476,7 +465,7 @@ class FusedAdam(torch.optim.Optimizer):
         return [(gi, [p for _, p in sorted(v, key=lambda kv: kv[0])], [k for k, _ in sorted(v, key=lambda kv: kv[0])])
                 for gi, v in by.items()]
 
-    def _lazy_launch(self, L, st, gi, ps, pos=None, owners=None, grads=None, ld_rg=0, n_owner=None) -> None:
+    def _lazy_launch(self, gi, ps, pos=None, owners=None, grads=None, ld_rg=0, n_owner=None) -> None:
         d = self._dev_state(gi, ps[0].device)
         sts = [self._lazy_state(p) for p in ps]
         for i in range(0, len(ps), 2):
@@ -485,35 +474,28 @@ class FusedAdam(torch.optim.Optimizer):
             p1, s1 = (ps[i + 1], sts[i + 1]) if two else (None, None)
             own = owners[i:i + 2] if owners is not None else [None, None]
             gr = grads[i:i + 2] if grads is not None else [None, None]
-
-            def ptr(t):
-                return t.data_ptr() if t is not None else None
-            check(L.mcl_adam_table_lazy(p0.data_ptr(), s0["exp_avg"].data_ptr(), s0["exp_avg_sq"].data_ptr(),
-                                        self._row_step(p0).data_ptr(), ptr(p1), ptr(s1["exp_avg"]) if two else None,
-                                        ptr(s1["exp_avg_sq"]) if two else None, ptr(self._row_step(p1)) if two else None,
-                                        p0.shape[0], p0.shape[1], ptr(pos), ptr(own[0]), ptr(own[1]) if two else None,
-                                        n_owner if n_owner is not None else p0.shape[0], ptr(gr[0]),
-                                        ptr(gr[1]) if two else None, ld_rg, d["step"].data_ptr(), d["hist"].data_ptr(),
-                                        HIST_LEN, st), "mcl_adam_table_lazy")
+            call("mcl_adam_table_lazy", p0, s0["exp_avg"], s0["exp_avg_sq"], self._row_step(p0), p1,
+                 s1["exp_avg"] if two else None, s1["exp_avg_sq"] if two else None, self._row_step(p1) if two else None,
+                 p0.shape[0], p0.shape[1], pos, own[0], own[1] if two else None, n_owner if n_owner is not None else p0.shape[0],
+                 gr[0], gr[1] if two else None, ld_rg, d["step"], d["hist"], HIST_LEN)
 
     def catch_up(self, pos: Tensor) -> None:
         """Bring the table rows a batch is about to gather up to the current step (pos: (B, 2) fp32 on the device, column 0
         indexes x_embed, column 1 y_embed).  Called by the model's forward in every mode; one small launch."""
         if not self._lazy_active() or not (self._lazy_dirty or torch.cuda.is_current_stream_capturing()):
             return                  # (a capture always records the launch: the flag describes the host's present, not a replay's)
-        L, st = _lib.lib(), ops._stream()
         for gi, ps, keys in self._lazy_groups():
             if keys != ["ix", "iy"] or ps[0].shape != ps[1].shape:
                 raise RuntimeError("lazy position tables expect x_embed and y_embed in one param group")
-            self._lazy_launch(L, st, gi, ps, pos=pos, n_owner=pos.shape[0])
+            self._lazy_launch(gi, ps, pos=pos, n_owner=pos.shape[0])
 
-    def _tables_step_lazy(self, L, st) -> None:
+    def _tables_step_lazy(self) -> None:
         """This step's update of the rows that received a data gradient (both tables, one launch): each is replayed
         through the previous step and then updated with g = wd*p + its gradient row."""
         dout, ix, iy = self._gathered()
         for gi, ps, keys in self._lazy_groups():
             rss = [ops.embed_rowgrad(dout, ix if k == "ix" else iy) for k in keys]
-            self._lazy_launch(L, st, gi, ps, owners=[r.owner_idx for r in rss], grads=[r.rows for r in rss],
+            self._lazy_launch(gi, ps, owners=[r.owner_idx for r in rss], grads=[r.rows for r in rss],
                               ld_rg=rss[0].rows.stride(0), n_owner=rss[0].rows.shape[0])
         self._lazy_dirty = True
 
@@ -524,11 +506,10 @@ class FusedAdam(torch.optim.Optimizer):
             return
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FusedAdam.materialize_tables() inside a graph capture")
-        L, st = _lib.lib(), ops._stream()
         for gi, ps, keys in self._lazy_groups():
             ps = [p for p in ps if self.state.get(p)]
             if ps:
-                self._lazy_launch(L, st, gi, ps)
+                self._lazy_launch(gi, ps)
         self._lazy_flushed_at = self._step_count
         self._lazy_dirty = False
         self.materialize_count += 1
@@ -618,7 +599,7 @@ class FusedAdam(torch.optim.Optimizer):
         s["g_dout"], s["g_ix"], s["g_iy"] = dout, ix, iy
         return dout, ix, iy
 
-    def _table_step(self, L, st, p, tab, gi: int) -> None:
+    def _table_step(self, p, tab, gi: int) -> None:
         state = self.state[p]
         if not state:
             state["exp_avg"] = torch.zeros_like(p)
@@ -630,9 +611,7 @@ class FusedAdam(torch.optim.Optimizer):
         rs = ops.embed_rowgrad(dout, ix if tab["key"] == "ix" else iy)
         B = rs.rows.shape[0]
         slot = tab["row_slot"]
-        check(L.mcl_row_slot_update(slot.data_ptr(), rs.owner_idx.data_ptr(), B, 1, st), "mcl_row_slot_update")
-        check(L.mcl_adam_table_step_dev(p.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
-                                        p.shape[0], p.shape[1], slot.data_ptr(), rs.rows.data_ptr(), rs.rows.stride(0),
-                                        self._dev_state(gi, p.device)["consts"].data_ptr(), st),
-              "mcl_adam_table_step_dev")
-        check(L.mcl_row_slot_update(slot.data_ptr(), rs.owner_idx.data_ptr(), B, 0, st), "mcl_row_slot_update")
+        call("mcl_row_slot_update", slot, rs.owner_idx, B, 1)
+        call("mcl_adam_table_step_dev", p, state["exp_avg"], state["exp_avg_sq"], p.shape[0],
+             p.shape[1], slot, rs.rows, rs.rows.stride(0), self._dev_state(gi, p.device)["consts"])
+        call("mcl_row_slot_update", slot, rs.owner_idx, B, 0)

@@ -34,9 +34,8 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib, ops
 from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload, write_json
-from ._lib import check
+from ._lib import call
 
 N_TOP_GENES = 1000       # hvg_her2st.py:24
 MAX_ROWS = 50000         # spots per slide (as mclstexp_amd.cluster)
@@ -196,7 +195,6 @@ def gene_stats(slides: Sequence[ArrayLike], colmaps: Optional[Sequence[Optional[
     a slide whose gene means are all equal, that holds no count or no defined dispersion raises ``ValueError``."""
     n_top_genes, cm, G = _stats_args(slides, colmaps, n_top_genes)
     dev = device("preprocess")
-    lib = _lib.lib()
     ss = _SlideSet(slides, dev)
     S = ss.S
     cm_d = upload(cm, dev) if cm is not None else None
@@ -207,10 +205,8 @@ def gene_stats(slides: Sequence[ArrayLike], colmaps: Optional[Sequence[Optional[
            "target_sum": e((S,), torch.float64)}
     work = e((int(ss.row_off[-1]),), torch.float64)
     status = e((S,), torch.int32)
-    check(lib.mcl_hvg_stats(*ss.args(), ops._p(cm_d), S, G, int(ss.rows.max()), n_top_genes, work.data_ptr(),
-                            res["means"].data_ptr(), res["dispersions"].data_ptr(), res["dispersions_norm"].data_ptr(),
-                            res["mean_bin"].data_ptr(), res["highly_variable"].data_ptr(), res["cutoff"].data_ptr(),
-                            res["target_sum"].data_ptr(), status.data_ptr(), ops._stream()), "mcl_hvg_stats")
+    call("mcl_hvg_stats", *ss.args(), cm_d, S, G, int(ss.rows.max()), n_top_genes, work, res["means"], res["dispersions"],
+         res["dispersions_norm"], res["mean_bin"], res["highly_variable"], res["cutoff"], res["target_sum"], status)
     st = status.cpu().numpy()                        # the one synchronisation
     if st.any():
         s = int(np.flatnonzero(st)[0])
@@ -235,12 +231,10 @@ def pool(highly_variable: ArrayLike, extra: Optional[ArrayLike] = None) -> Tuple
             raise ValueError(f"extra: gene indices must lie in 0 .. {G - 1}")
         ex = ex.astype(np.int32)
     dev = device("preprocess")
-    lib = _lib.lib()
     hv = hv.to(dev).contiguous()
     ex_d = upload(ex, dev) if ex is not None and ex.size else None
     uni, inter = torch.empty((G,), device=dev, dtype=torch.bool), torch.empty((G,), device=dev, dtype=torch.bool)
-    check(lib.mcl_hvg_pool(hv.data_ptr(), S, G, ops._p(ex_d), int(ex.size) if ex_d is not None else 0, uni.data_ptr(),
-                           inter.data_ptr(), ops._stream()), "mcl_hvg_pool")
+    call("mcl_hvg_pool", hv, S, G, ex_d, int(ex.size) if ex_d is not None else 0, uni, inter)
     return uni, inter
 
 
@@ -260,12 +254,10 @@ def expression_matrices(slides: Sequence[ArrayLike], colmaps: Optional[Sequence[
     S, K = len(slides), int(g.size)
     sel = cm[:, g] if cm is not None else np.broadcast_to(g.astype(np.int32), (S, K))
     dev = device("preprocess")
-    lib = _lib.lib()
     ss = _SlideSet(slides, dev)
     sel_d = upload(np.asarray(sel, dtype=np.int32), dev)
     out = torch.empty((K * int(ss.row_off[-1]),), device=dev, dtype=torch.float32)
-    check(lib.mcl_expression_matrices(*ss.args(), sel_d.data_ptr(), S, K, int(ss.rows.max()), float(RESCALE),
-                                      out.data_ptr(), ops._stream()), "mcl_expression_matrices")
+    call("mcl_expression_matrices", *ss.args(), sel_d, S, K, int(ss.rows.max()), float(RESCALE), out)
     return [out[K * int(ss.row_off[s]):K * int(ss.row_off[s + 1])].view(K, int(ss.rows[s])) for s in range(S)]
 
 

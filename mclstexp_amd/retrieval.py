@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, ops
 from ._arrays import ArrayLike, Tensor, device, matrix
-from ._lib import check
+from ._lib import call
 
 # upper bound of the (Q_chunk, N) fp32 similarity workspace
 SIM_WORKSPACE_BYTES = 1 << 30
@@ -42,8 +42,7 @@ def l2_normalize(x: Tensor) -> Tensor:
     """F.normalize(x, p=2, dim=-1) (evel_her2st.py:78-79)."""
     x = ops._rowmajor(x, "x")
     y = torch.empty_like(x, memory_format=torch.contiguous_format)
-    check(_lib.lib().mcl_l2_normalize_rows(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), x.shape[0],
-                                           x.shape[1], ops._stream()), "mcl_l2_normalize_rows")
+    call("mcl_l2_normalize_rows", x, x.stride(0), y, y.stride(0), x.shape[0], x.shape[1])
     return y
 
 
@@ -66,8 +65,7 @@ def topk_rows(sim: Tensor, k: int) -> Tuple[Tensor, Tensor]:
         raise RuntimeError(f"top_k={k} out of range for {n} keys")
     values = torch.empty((rows, k), device=sim.device, dtype=torch.float32)
     indices = torch.empty((rows, k), device=sim.device, dtype=torch.int64)
-    check(_lib.lib().mcl_topk_rows(sim.data_ptr(), sim.stride(0), rows, n, k, values.data_ptr(), indices.data_ptr(),
-                                   ops._stream()), "mcl_topk_rows")
+    call("mcl_topk_rows", sim, sim.stride(0), rows, n, k, values, indices)
     return values, indices
 
 
@@ -109,7 +107,6 @@ def find_matches_filtered(query: Tensor, keys: Tensor, top_k: int) -> Tuple[Tens
     q, p = query.shape
     n = keys.shape[0]
     dev = query.device
-    L = _lib.lib()
     ns, step, r, cap = _filter_plan(n, top_k)
     sample = keys[::step][:ns]                                   # strided view: rows stay unit-stride
     values = torch.empty((q, top_k), device=dev, dtype=torch.float32)
@@ -129,8 +126,7 @@ def find_matches_filtered(query: Tensor, keys: Tensor, top_k: int) -> Tuple[Tens
                      compute=_lib.COMPUTE_F32, filt=(thr, cnt, cval, cidx))
         v, i = values[q0:q1], indices[q0:q1]
         tie = torch.zeros((qc,), device=dev, dtype=torch.int32)
-        check(L.mcl_topk_rows_indexed(cval.data_ptr(), cap, cidx.data_ptr(), cap, qc, cap, top_k, v.data_ptr(), i.data_ptr(),
-                                      tie.data_ptr(), ops._stream()), "mcl_topk_rows_indexed")
+        call("mcl_topk_rows_indexed", cval, cap, cidx, cap, qc, cap, top_k, v, i, tie)
         bad = ((cnt < top_k) | (cnt > cap) | (tie != 0)).nonzero().flatten()  # (host sync: the retrieval returns to the host anyway)
         for b0 in range(0, int(bad.numel()), redo_chunk):
             rows = bad[b0:b0 + redo_chunk]
@@ -195,10 +191,8 @@ def weighted_average_device(spot_key: ArrayLike, expression_key: Optional[ArrayL
             raise RuntimeError("expression_key and spot_key must have one row per training spot")
         genes = expr_t.shape[1]
         expr_out = torch.empty((q, genes), device=key.device, dtype=torch.float32)
-    check(_lib.lib().mcl_knn_weighted_average(
-        key.data_ptr(), key.stride(0), ops._p(expr_t), expr_t.stride(0) if expr_t is not None else 0,
-        qry.data_ptr(), qry.stride(0), idx.data_ptr(), q, k, key.shape[1], genes, int(ord), emb.data_ptr(),
-        ops._p(expr_out), ops._stream()), "mcl_knn_weighted_average")
+    call("mcl_knn_weighted_average", key, key.stride(0), expr_t, expr_t.stride(0) if expr_t is not None else 0,
+         qry, qry.stride(0), idx, q, k, key.shape[1], genes, int(ord), emb, expr_out)
     return emb, expr_out
 
 
@@ -232,10 +226,8 @@ def combine_device(spot_key: ArrayLike, expression_key: Optional[ArrayLike], ima
             raise RuntimeError("expression_key and spot_key must have one row per training spot")
         genes = expr_t.shape[1]
         expr_out = torch.empty((q, genes), device=key.device, dtype=torch.float32)
-    check(_lib.lib().mcl_knn_combine(
-        key.data_ptr(), key.stride(0), ops._p(expr_t), expr_t.stride(0) if expr_t is not None else 0,
-        qry.data_ptr(), qry.stride(0), idx.data_ptr(), q, k, key.shape[1], genes, COMBINE_MODES[method], emb.data_ptr(),
-        ops._p(expr_out), ops._stream()), "mcl_knn_combine")
+    call("mcl_knn_combine", key, key.stride(0), expr_t, expr_t.stride(0) if expr_t is not None else 0,
+         qry, qry.stride(0), idx, q, k, key.shape[1], genes, COMBINE_MODES[method], emb, expr_out)
     return emb, expr_out
 
 

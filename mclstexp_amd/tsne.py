@@ -35,9 +35,9 @@ from typing import Dict, List, Optional, Sequence, Union
 import numpy as np
 import torch
 
-from . import _arrays, _lib, cluster
+from . import _arrays, cluster
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, stack_rows, upload
-from ._lib import check
+from ._lib import call
 
 MAX_DIM = 64             # csrc/tsne.hip
 MAX_ROWS = 16384         # per segment: one row of distances lives in LDS
@@ -49,10 +49,6 @@ PATIENCE = (250, 300)    # iterations without progress: the first phase, then TS
 MIN_GRAD_NORM = 1e-7
 MOMENTUM = (0.5, 0.8)
 OUT_FILE = "X_tsne.npy"
-
-
-def _stream() -> int:
-    return torch.cuda.current_stream().cuda_stream
 
 
 # ------------------------------------------------------------------------------------------------------- host rules
@@ -174,26 +170,19 @@ class _Plan:
         self.poff = cumulative_offsets(seg * seg)
         self.S, self.rows = int(seg.size), int(off[-1])
         self.min_n, self.max_n, self.pairs = int(seg.min()), int(seg.max()), int(self.poff[-1])
-        self.lib = _lib.lib()
         self.off_d, self.poff_d = upload(off, dev), upload(self.poff, dev)
-        self.work = empty(dev)((max(int(self.lib.mcl_tsne_workspace_doubles(self.rows, self.S)), 8),), torch.float64)
+        self.work = empty(dev)((max(int(call("mcl_tsne_workspace_doubles", self.rows, self.S)), 8),), torch.float64)
 
     def affinities(self, xd: Tensor, perplexity: float, f32: bool, P: Tensor, beta: Tensor) -> None:
-        check(self.lib.mcl_tsne_affinities(xd.data_ptr(), xd.stride(0), FLOAT_CODE[xd.dtype], int(xd.shape[1]),
-                                           self.off_d.data_ptr(), self.poff_d.data_ptr(), self.S, self.rows, self.min_n,
-                                           self.max_n, self.pairs, float(perplexity), int(bool(f32)), self.work.data_ptr(),
-                                           P.data_ptr(), beta.data_ptr(), _stream()), "mcl_tsne_affinities")
+        call("mcl_tsne_affinities", xd, xd.stride(0), FLOAT_CODE[xd.dtype], int(xd.shape[1]), self.off_d, self.poff_d,
+             self.S, self.rows, self.min_n, self.max_n, self.pairs, float(perplexity), bool(f32), self.work, P, beta)
 
     def gradient(self, P: Tensor, Y: Tensor, params: Tensor, want_kl: bool, grad: Tensor, kl: Tensor) -> None:
-        check(self.lib.mcl_tsne_gradient(P.data_ptr(), self.poff_d.data_ptr(), Y.data_ptr(), self.off_d.data_ptr(), self.S,
-                                         self.rows, self.min_n, self.max_n, self.pairs, params.data_ptr(), int(want_kl),
-                                         self.work.data_ptr(), grad.data_ptr(), kl.data_ptr(), _stream()),
-              "mcl_tsne_gradient")
+        call("mcl_tsne_gradient", P, self.poff_d, Y, self.off_d, self.S, self.rows,
+             self.min_n, self.max_n, self.pairs, params, want_kl, self.work, grad, kl)
 
     def update(self, grad: Tensor, params: Tensor, Y: Tensor, upd: Tensor, gains: Tensor, norm2: Tensor) -> None:
-        check(self.lib.mcl_tsne_update(grad.data_ptr(), self.off_d.data_ptr(), self.S, self.rows, self.min_n, self.max_n,
-                                       params.data_ptr(), Y.data_ptr(), upd.data_ptr(), gains.data_ptr(), norm2.data_ptr(),
-                                       _stream()), "mcl_tsne_update")
+        call("mcl_tsne_update", grad, self.off_d, self.S, self.rows, self.min_n, self.max_n, params, Y, upd, gains, norm2)
 
 
 def _check_x(x: ArrayLike, offsets, perplexity: float):

@@ -36,10 +36,10 @@ from typing import Dict, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _arrays, _lib, neighbors
+from . import _arrays, neighbors
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload
-from ._lib import check
-from .neighbors import _dense, _stream
+from ._lib import call
+from .neighbors import _dense
 
 MAX_ROWS = 16384         # csrc/umap.hip
 MAX_SEGMENTS = 65535
@@ -191,33 +191,27 @@ def layout(graph: Dict[str, object], init: Union[str, ArrayLike] = "pca", x: Opt
     if a is None:
         a, b = find_ab_params(spread, min_dist)
     dev = device("umap")
-    lib = _lib.lib()
     e = empty(dev)
     indptr = _dense(graph["indptr"], "indptr", (rows + S,), torch.int64, dev)
     indices = _dense(graph["indices"], "indices", (total,), torch.int32, dev) if total else e((1,), torch.int32)
     data = _dense(graph["data"], "data", (total,), torch.float64, dev) if total else e((1,), torch.float64)
     off_d, nnz_off_d, epochs_d = upload(off, dev), upload(nnz_off, dev), upload(epochs, dev)
-    work = e((max(int(lib.mcl_umap_workspace_bytes(total, S)), 8) // 8 + 1,), torch.float64)
+    work = e((max(int(call("mcl_umap_workspace_bytes", total, S)), 8) // 8 + 1,), torch.float64)
     counters = e((S, 2), torch.int64)
     Y = [e((rows, 2), torch.float64), e((rows, 2), torch.float64)]
     sizes = (S, rows, int(seg.min()), int(seg.max()))
     max_epochs, rate, seed64 = int(epochs.max()), int(negative_sample_rate), int(seed) & _MASK
     if isinstance(init, str):
         xd = matrix(x, "x", dev, FLOAT_CODE, torch.float64) if init == "pca" else None
-        check(lib.mcl_umap_init(INITS.index(init), xd.data_ptr() if xd is not None else None,
-                                xd.stride(0) if xd is not None else 0, FLOAT_CODE[xd.dtype] if xd is not None else 1,
-                                int(xd.shape[1]) if xd is not None else 0, off_d.data_ptr(), *sizes, seed64,
-                                Y[0].data_ptr(), _stream()), "mcl_umap_init")
+        call("mcl_umap_init", INITS.index(init), xd, xd.stride(0) if xd is not None else 0,
+             FLOAT_CODE[xd.dtype] if xd is not None else 1,
+             int(xd.shape[1]) if xd is not None else 0, off_d, *sizes, seed64, Y[0])
     else:
         Y[0].copy_(_dense(init, "init", (rows, 2), torch.float64, dev))
-    check(lib.mcl_umap_prepare(data.data_ptr(), nnz_off_d.data_ptr(), epochs_d.data_ptr(), S, total,
-                               int(np.diff(nnz_off).max()), max_epochs, rate, work.data_ptr(), counters.data_ptr(),
-                               _stream()), "mcl_umap_prepare")
+    call("mcl_umap_prepare", data, nnz_off_d, epochs_d, S, total, int(np.diff(nnz_off).max()), max_epochs, rate, work, counters)
     count = max_epochs if stop_after is None else min(int(stop_after), max_epochs)
-    check(lib.mcl_umap_epochs(0, count, indptr.data_ptr(), indices.data_ptr(), off_d.data_ptr(), nnz_off_d.data_ptr(),
-                              epochs_d.data_ptr(), *sizes, total, max_epochs, float(a), float(b), float(gamma), float(alpha),
-                              rate, seed64, work.data_ptr(), Y[0].data_ptr(), Y[1].data_ptr(), counters.data_ptr(),
-                              _stream()), "mcl_umap_epochs")
+    call("mcl_umap_epochs", 0, count, indptr, indices, off_d, nnz_off_d, epochs_d, *sizes, total, max_epochs,
+         float(a), float(b), float(gamma), float(alpha), rate, seed64, work, Y[0], Y[1], counters)
     c = counters.cpu().numpy()                         # the one synchronisation
     return {"embedding": Y[count & 1], "attractive_samples": c[:, 0].copy(), "negative_samples": c[:, 1].copy(),
             "n_epochs": epochs, "a": float(a), "b": float(b), "offsets": off}

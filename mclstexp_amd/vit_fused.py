@@ -20,7 +20,7 @@ import os
 import torch
 
 from . import _lib, ops
-from ._lib import check
+from ._lib import call
 from . import densenet_fused as _dn
 from .densenet_fused import _direct_grad_ok, _ws
 
@@ -33,8 +33,7 @@ GELU_GRAD_OUT, AUX_IS_GRAD = 32, 64           # fc1 stores gelu'(pre-activation)
 KERNEL_LOCKSTEP, KERNEL_NO_PIPE, KERNEL_PIPE = 1 << 7, 2 << 7, 3 << 7
 
 
-def _st() -> int:
-    return torch.cuda.current_stream().cuda_stream
+_st = _lib.current_stream                # (tests that call the C ABI directly pass it)
 
 
 def _ptr(t: Optional[Tensor], off: int = 0) -> Optional[int]:
@@ -47,14 +46,12 @@ def gemm(A: Tensor, B: Tensor, C: Tensor, M: int, N: int, K: int, lda: int, ldb:
          r_off: int = 0, aux: Optional[Tensor] = None, ldaux: int = 0, pre_out: Optional[Tensor] = None, ldp: int = 0,
          ksplit: int = 1, accumulate: bool = False) -> None:
     """mcl_gemm_bf16 with element offsets / strides (see include/mclstexp_hip.h)."""
-    L = _lib.lib()
     ws = None
     if ksplit > 1:
-        ws = _ws(L.mcl_gemm_bf16_workspace_floats(M, ldc, ksplit), C.device)
-    check(L.mcl_gemm_bf16(_ptr(A, a_off), lda, sA[0], _ptr(B, b_off), ldb, sB[0], _ptr(C, c_off), ldc, sC[0], M, N, K,
-                          batch, batch2, sA[1], sB[1], sC[1], alpha, flags, _ptr(bias), _ptr(resid, r_off), ldr, sRb,
-                          _ptr(aux), ldaux, _ptr(pre_out), ldp, ksplit, _ptr(ws), int(accumulate), _st()),
-          "mcl_gemm_bf16")
+        ws = _ws(call("mcl_gemm_bf16_workspace_floats", M, ldc, ksplit), C.device)
+    call("mcl_gemm_bf16", _ptr(A, a_off), lda, sA[0], _ptr(B, b_off), ldb, sB[0],
+         _ptr(C, c_off), ldc, sC[0], M, N, K, batch, batch2, sA[1], sB[1], sC[1], alpha, flags,
+         bias, _ptr(resid, r_off), ldr, sRb, aux, ldaux, pre_out, ldp, ksplit, ws, accumulate)
 
 
 def _w16(w: Tensor) -> Tensor:
@@ -92,8 +89,7 @@ def _patch_weight_matrix(w: Tensor, dt: torch.dtype) -> Tensor:
         return _w16(wd.reshape(D, C * p * p))
     out = torch.empty((D, C * p * p), device=w.device, dtype=dt)
     s0, s1, s2, s3 = wd.stride()
-    check(_lib.lib().mcl_strided4_f32(wd.data_ptr(), D, C, p, p, s0, s1, s2, s3, out.data_ptr(), C * p * p, p * p, p, 1,
-                                      0 if dt == torch.float32 else 1, 0, _st()), "mcl_strided4_f32")
+    call("mcl_strided4_f32", wd, D, C, p, p, s0, s1, s2, s3, out, C * p * p, p * p, p, 1, 0 if dt == torch.float32 else 1, 0)
     return out
 
 
@@ -112,8 +108,7 @@ def _patch_weight_grad(dy: Tensor, patches: Tensor, w: Tensor, rows: int):
     if _direct_grad_ok(w):
         g = w.grad
         s0, s1, s2, s3 = g.stride()
-        check(_lib.lib().mcl_strided4_f32(gw.data_ptr(), D, C, p, p, K0, p * p, p, 1, g.data_ptr(), s0, s1, s2, s3, 0, 1, _st()),
-              "mcl_strided4_f32")
+        call("mcl_strided4_f32", gw, D, C, p, p, K0, p * p, p, 1, g, s0, s1, s2, s3, 0, 1)
         return None
     return gw.view(D, C, p, p)
 
@@ -169,10 +164,8 @@ def linear_wgrad(dy: Tensor, x: Tensor, w: Tensor, rows: int):
 def bias_grad(dy: Tensor, b: Tensor, rows: int):
     D = b.numel()
     tgt, acc, ret = _grad_target(b)
-    L = _lib.lib()
-    ws = _ws(L.mcl_colred_workspace_floats(rows, D), dy.device)
-    check(L.mcl_colsum_bf16(dy.data_ptr(), dy.shape[-1], rows, D, ws.data_ptr(), tgt.data_ptr(), int(acc), _st()),
-          "mcl_colsum_bf16")
+    ws = _ws(call("mcl_colred_workspace_floats", rows, D), dy.device)
+    call("mcl_colsum_bf16", dy, dy.shape[-1], rows, D, ws, tgt, acc)
     return ret
 
 
@@ -181,8 +174,7 @@ def ln_fwd(x: Tensor, ln: torch.nn.LayerNorm, rows: int):
     y = torch.empty_like(x)
     mean = torch.empty(rows, device=x.device, dtype=torch.float32)
     rstd = torch.empty(rows, device=x.device, dtype=torch.float32)
-    check(_lib.lib().mcl_ln_bf16_fwd(x.data_ptr(), D, ln.weight.data_ptr(), ln.bias.data_ptr(), y.data_ptr(), D,
-                                     mean.data_ptr(), rstd.data_ptr(), rows, D, float(ln.eps), _st()), "mcl_ln_bf16_fwd")
+    call("mcl_ln_bf16_fwd", x, D, ln.weight, ln.bias, y, D, mean, rstd, rows, D, float(ln.eps))
     return y, mean, rstd
 
 
@@ -193,11 +185,9 @@ def ln_bwd(dy: Tensor, x: Tensor, ln: torch.nn.LayerNorm, mean: Tensor, rstd: Te
     tg, acc_g, ret_g = _grad_target(ln.weight)
     tb, acc_b, ret_b = _grad_target(ln.bias)
     assert acc_g == acc_b
-    L = _lib.lib()
-    ws = _ws(L.mcl_colred_workspace_floats(rows, D), x.device)
-    check(L.mcl_ln_bf16_bwd(dy.data_ptr(), D, x.data_ptr(), D, ln.weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
-                            _ptr(dx_add), D if dx_add is not None else 0, dx.data_ptr(), D, ws.data_ptr(), tg.data_ptr(),
-                            tb.data_ptr(), int(acc_g), rows, D, _st()), "mcl_ln_bf16_bwd")
+    ws = _ws(call("mcl_colred_workspace_floats", rows, D), x.device)
+    call("mcl_ln_bf16_bwd", dy, D, x, D, ln.weight, mean, rstd, dx_add,
+         D if dx_add is not None else 0, dx, D, ws, tg, tb, acc_g, rows, D)
     return dx, ret_g, ret_b
 
 
@@ -220,21 +210,20 @@ class ViTFn(torch.autograd.Function):
         dh = D // heads
         M = B * T
         Tp = (T + 15) // 16 * 16
-        L = _lib.lib()
         img = image if image.dtype == torch.float32 else image.float()
         # patches with a zero row at the class-token position: (B, T, K0); the weight gradient of the patch embedding
         # is then ONE reduction over all B*T rows.  Token assembly on own kernels (csrc/glue.hip): no ATen launch.
         patches = torch.empty((B, T, K0), device=dev, dtype=BF)
-        check(L.mcl_vit_patchify_tokens(img.data_ptr(), img.stride(0), img.stride(1), img.stride(2), img.stride(3), B, H, W, p,
-                                        patches.data_ptr(), 1, 0, _st()), "mcl_vit_patchify_tokens")
+        call("mcl_vit_patchify_tokens", img, img.stride(0), img.stride(1),
+             img.stride(2), img.stride(3), B, H, W, p, patches, 1, 0)
         pos, cls = _dense_f32(vit.pos_embed), _dense_f32(vit.cls_token)
         pos16 = torch.empty((T, D), device=dev, dtype=BF)
-        check(L.mcl_cast_f32_to_bf16(pos.data_ptr(), D, pos16.data_ptr(), D, T, D, _st()), "mcl_cast_f32_to_bf16")
+        call("mcl_cast_f32_to_bf16", pos, D, pos16, D, T, D)
         x = torch.empty((B, T, D), device=dev, dtype=BF)
         wpe = _patch_weight_matrix(pe.weight, BF)                            # (D, K0), (c, iy, ix) order whatever the memory format
         gemm(patches, wpe, x, npatch, D, K0, K0, K0, D, a_off=K0, c_off=D, batch=B, sA=(T * K0, 0), sC=(T * D, 0),
              bias=pe.bias, resid=pos16, ldr=D, sRb=0, r_off=D)
-        check(L.mcl_vit_cls_row(cls.data_ptr(), pos.data_ptr(), x.data_ptr(), B, T, D, 1, _st()), "mcl_vit_cls_row")
+        call("mcl_vit_cls_row", cls, pos, x, B, T, D, 1)
         saved = []
         scale = dh ** -0.5
         fused_attn = FUSED_ATTN and dh == 64 and T <= 224
@@ -248,12 +237,12 @@ class ViTFn(torch.autograd.Function):
                 # softmax(q k^T scale) v per image and head in ONE launch, no (B heads, T, T) tensor (csrc/vit_attention.hip);
                 # P below is the row log-sum-exp, all the backward needs
                 P = torch.empty((B * heads, T), device=dev, dtype=torch.float32)
-                check(L.mcl_vit_attn_fwd(qkv.data_ptr(), o.data_ptr(), P.data_ptr(), B, T, heads, scale, _st()), "mcl_vit_attn_fwd")
+                call("mcl_vit_attn_fwd", qkv, o, P, B, T, heads, scale)
             else:
                 P = torch.empty((B * heads, T, Tp), device=dev, dtype=BF)
                 gemm(qkv, qkv, P, T, T, dh, 3 * D, 3 * D, Tp, b_off=D, batch=B * heads, batch2=heads,
                      sA=(T * 3 * D, dh), sB=(T * 3 * D, dh), sC=(heads * T * Tp, T * Tp), alpha=scale)
-                check(L.mcl_softmax_bf16_fwd(P.data_ptr(), Tp, B * heads * T, T, _st()), "mcl_softmax_bf16_fwd")
+                call("mcl_softmax_bf16_fwd", P, Tp, B * heads * T, T)
                 gemm(P, qkv, o, T, dh, T, Tp, 3 * D, D, flags=B_KM, b_off=2 * D, batch=B * heads, batch2=heads,
                      sA=(heads * T * Tp, T * Tp), sB=(T * 3 * D, dh), sC=(T * D, dh))
             x1 = torch.empty_like(x)
@@ -268,7 +257,7 @@ class ViTFn(torch.autograd.Function):
             saved += [x, mean1, rstd1, u1, qkv, P, o, x1, mean2, rstd2, u2, pre, h1]
             x = x2
         feat = torch.empty((B, D), device=dev, dtype=torch.float32)      # global_pool='avg' over the patch tokens
-        check(L.mcl_vit_token_mean_fwd(x.data_ptr(), feat.data_ptr(), B, T, D, 1, _st()), "mcl_vit_token_mean_fwd")
+        call("mcl_vit_token_mean_fwd", x, feat, B, T, D, 1)
         ctx.save_for_backward(patches, *saved)
         ctx.vit = vit
         ctx.dims = (B, T, D, K0, heads, dh, Tp, npatch)
@@ -283,12 +272,11 @@ class ViTFn(torch.autograd.Function):
         t = ctx.saved_tensors
         patches, saved = t[0], t[1:]
         dev = dfeat.device
-        L = _lib.lib()
         from . import densenet_fused as _dn
         scale = dh ** -0.5
         dx = torch.empty((B, T, D), device=dev, dtype=BF)
         dfeat = dfeat if (dfeat.dtype == torch.float32 and dfeat.is_contiguous()) else dfeat.float().contiguous()
-        check(L.mcl_vit_token_mean_bwd(dfeat.data_ptr(), dx.data_ptr(), B, T, D, 1, _st()), "mcl_vit_token_mean_bwd")
+        call("mcl_vit_token_mean_bwd", dfeat, dx, B, T, D, 1)
         grads = {}
         nblk = len(vit.blocks)
         for li in range(nblk - 1, -1, -1):
@@ -314,8 +302,7 @@ class ViTFn(torch.autograd.Function):
             if ctx.fused_attn:
                 # P = the forward's row log-sum-exp: dq, dk, dv in two launches, probabilities recomputed on chip
                 dsum = torch.empty((nb, T), device=dev, dtype=torch.float32)
-                check(L.mcl_vit_attn_bwd(qkv.data_ptr(), o.data_ptr(), do.data_ptr(), P.data_ptr(), dsum.data_ptr(),
-                                         dqkv.data_ptr(), B, T, heads, scale, _st()), "mcl_vit_attn_bwd")
+                call("mcl_vit_attn_bwd", qkv, o, do, P, dsum, dqkv, B, T, heads, scale)
             else:
                 sP = (heads * T * Tp, T * Tp)
                 sQ = (T * 3 * D, dh)
@@ -324,8 +311,7 @@ class ViTFn(torch.autograd.Function):
                      sA=sP, sB=sO, sC=sQ)                                                   # dV = P^T dO
                 dP = torch.empty((B * heads, T, Tp), device=dev, dtype=BF)
                 gemm(do, qkv, dP, T, T, dh, D, 3 * D, Tp, b_off=2 * D, batch=nb, batch2=heads, sA=sO, sB=sQ, sC=sP)   # dO V^T
-                check(L.mcl_softmax_bf16_bwd(P.data_ptr(), dP.data_ptr(), Tp, B * heads * T, T, scale, _st()),
-                      "mcl_softmax_bf16_bwd")
+                call("mcl_softmax_bf16_bwd", P, dP, Tp, B * heads * T, T, scale)
                 gemm(dP, qkv, dqkv, T, dh, T, Tp, 3 * D, 3 * D, flags=B_KM, b_off=D, batch=nb, batch2=heads,
                      sA=sP, sB=sQ, sC=sQ)                                                   # dQ = dS K
                 gemm(dP, qkv, dqkv, T, dh, T, Tp, 3 * D, 3 * D, flags=A_KM | B_KM, c_off=D, batch=nb, batch2=heads,
@@ -339,12 +325,11 @@ class ViTFn(torch.autograd.Function):
         # embeddings: position table and class token (fp32 sums over the batch), patch projection
         tp, accp, retp = _grad_target(vit.pos_embed)
         tc, accc, retc = _grad_target(vit.cls_token)
-        check(L.mcl_vit_pos_grad(dx.data_ptr(), tp.data_ptr(), tc.data_ptr(), B, T, D, 1, (1 if accp else 0) | (2 if accc else 0),
-                                 _st()), "mcl_vit_pos_grad")
+        call("mcl_vit_pos_grad", dx, tp, tc, B, T, D, 1, (1 if accp else 0) | (2 if accc else 0))
         grads[vit.pos_embed], grads[vit.cls_token] = retp, retc
         pe = vit.patch_embed.proj
         # class-token rows carry no patch: zeroed in place (dx is dead after this) for the bias gradient; their patch rows are zero
-        check(L.mcl_vit_zero_cls_rows(dx.data_ptr(), B, T, D, 1, _st()), "mcl_vit_zero_cls_rows")
+        call("mcl_vit_zero_cls_rows", dx, B, T, D, 1)
         grads[pe.weight] = _patch_weight_grad(dx, patches, pe.weight, M)
         grads[pe.bias] = bias_grad(dx, pe.bias, M)
         _dn._side_join(dev)
@@ -358,21 +343,19 @@ class _EmbedF32Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, w, b, cls, pos, p):
-        L = _lib.lib()
         B, Cin, H, W = img.shape
         nph, npw = H // p, W // p
         npatch, T = nph * npw, nph * npw + 1
         D, K0 = w.shape[0], Cin * p * p
         dev = img.device
         patches = torch.empty((B * npatch, K0), device=dev, dtype=torch.float32)
-        check(L.mcl_vit_patchify_tokens(img.data_ptr(), img.stride(0), img.stride(1), img.stride(2), img.stride(3), B, H, W, p,
-                                        patches.data_ptr(), 0, 1, _st()), "mcl_vit_patchify_tokens")
+        call("mcl_vit_patchify_tokens", img, img.stride(0), img.stride(1),
+             img.stride(2), img.stride(3), B, H, W, p, patches, 0, 1)
         wm = _patch_weight_matrix(w, torch.float32)
         with ops.forced_compute(_lib.COMPUTE_F32):
             tok, _ = ops.linear_fwd(patches, wm, b.detach() if b is not None else None)
         x = torch.empty((B * T, D), device=dev, dtype=torch.float32)
-        check(L.mcl_vit_assemble_f32(tok.data_ptr(), _dense_f32(cls).data_ptr(), _dense_f32(pos).data_ptr(), x.data_ptr(), B, T, D,
-                                     _st()), "mcl_vit_assemble_f32")
+        call("mcl_vit_assemble_f32", tok, _dense_f32(cls), _dense_f32(pos), x, B, T, D)
         ctx.save_for_backward(patches)
         ctx.params = (w, b, cls, pos)
         ctx.dims = (B, T, D, Cin, p)
@@ -383,16 +366,14 @@ class _EmbedF32Fn(torch.autograd.Function):
         (patches,) = ctx.saved_tensors
         w, b, cls, pos = ctx.params
         B, T, D, Cin, p = ctx.dims
-        L = _lib.lib()
         dx = ops._rowmajor(dx, "dx")
         if dx.stride(0) != D:
             raise RuntimeError("vit_fused: the token gradient must be a dense (B*T, D) matrix")
         dtok = torch.empty((B * (T - 1), D), device=dx.device, dtype=torch.float32)
-        check(L.mcl_vit_tokens_extract(dx.data_ptr(), dtok.data_ptr(), B, T, D, 0, _st()), "mcl_vit_tokens_extract")
+        call("mcl_vit_tokens_extract", dx, dtok, B, T, D, 0)
         tp, accp, retp = _grad_target(pos)
         tc, accc, retc = _grad_target(cls)
-        check(L.mcl_vit_pos_grad(dx.data_ptr(), tp.data_ptr(), tc.data_ptr(), B, T, D, 0, (1 if accp else 0) | (2 if accc else 0),
-                                 _st()), "mcl_vit_pos_grad")
+        call("mcl_vit_pos_grad", dx, tp, tc, B, T, D, 0, (1 if accp else 0) | (2 if accc else 0))
         with ops.forced_compute(_lib.COMPUTE_F32):
             K0 = Cin * p * p
             if w.is_contiguous() and _direct_grad_ok(w) and w.grad.is_contiguous():
@@ -404,8 +385,7 @@ class _EmbedF32Fn(torch.autograd.Function):
                 if _direct_grad_ok(w):
                     g = w.grad
                     s0, s1, s2, s3 = g.stride()
-                    check(L.mcl_strided4_f32(gw.data_ptr(), D, Cin, p, p, K0, p * p, p, 1, g.data_ptr(), s0, s1, s2, s3, 0, 1, _st()),
-                          "mcl_strided4_f32")
+                    call("mcl_strided4_f32", gw, D, Cin, p, p, K0, p * p, p, 1, g, s0, s1, s2, s3, 0, 1)
                     dw = None
                 else:
                     dw = gw.view(D, Cin, p, p)
@@ -423,7 +403,7 @@ class _TokenMeanF32Fn(torch.autograd.Function):
         if x.stride(0) != D:
             raise RuntimeError("vit_fused: the token matrix must be dense")
         feat = torch.empty((B, D), device=x.device, dtype=torch.float32)
-        check(_lib.lib().mcl_vit_token_mean_fwd(x.data_ptr(), feat.data_ptr(), B, T, D, 0, _st()), "mcl_vit_token_mean_fwd")
+        call("mcl_vit_token_mean_fwd", x, feat, B, T, D, 0)
         ctx.dims = (B, T, D)
         return feat
 
@@ -432,7 +412,7 @@ class _TokenMeanF32Fn(torch.autograd.Function):
         B, T, D = ctx.dims
         dfeat = dfeat if (dfeat.dtype == torch.float32 and dfeat.is_contiguous()) else dfeat.float().contiguous()
         dx = torch.empty((B * T, D), device=dfeat.device, dtype=torch.float32)
-        check(_lib.lib().mcl_vit_token_mean_bwd(dfeat.data_ptr(), dx.data_ptr(), B, T, D, 0, _st()), "mcl_vit_token_mean_bwd")
+        call("mcl_vit_token_mean_bwd", dfeat, dx, B, T, D, 0)
         return dx, None, None
 
 

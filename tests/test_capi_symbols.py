@@ -42,12 +42,115 @@ def test_missing_library_fails_loudly(tmp_path):
 def test_argument_errors_without_gpu():
     """Argument validation happens before any launch, so it is checkable on CPU."""
     import ctypes as C
-    from mclstexp_amd import _lib
+    from mclstexp_amd import _lib, build
+    if not os.path.exists(_lib.LIB_PATH):
+        build.build(verbose=False)
     lib = _lib.load()
     a = _lib.gemm_args()
     assert lib.mcl_gemm(C.byref(a), None) == -1
     assert lib.mcl_layernorm_fwd(None, 0, None, None, None, 0, None, None, 0, 0, 1e-5, None) == -1
     assert lib.mcl_adam_step(None, None, None, None, 0, 1e-4, .9, .999, 1e-8, 1e-3, .1, .001, None) == -1
+
+
+# ---------------------------------------------------------------- prototypes: header == ctypes table, type by type
+_ARG_KIND = {"int32_t": "i32", "int": "i32", "int64_t": "i64", "uint32_t": "u32", "uint64_t": "u64", "float": "f32",
+             "double": "f64", "mcl_stream_t": "stream"}
+
+
+def header_prototypes():
+    """{name: (return kind, [argument kinds])} for every function include/mclstexp_hip.h declares.  Kinds: 'ptr', 'i32'
+    (int32_t / int), 'i64', 'u32', 'u64', 'f32', 'f64', 'stream'."""
+    text = open(os.path.join(ROOT, "include", "mclstexp_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", "", text)
+
+    def kind(decl, named):
+        decl = " ".join(decl.replace("*", " * ").split())
+        if "*" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        if named:
+            assert len(words) == 2, f"unnamed or unreadable parameter: {decl!r}"
+        return _ARG_KIND[words[0]]
+
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s\*]+?)\b(mcl_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", text):
+        params = [q for q in (q.strip() for q in params.split(",")) if q and q != "void"]
+        assert name not in out, f"{name} is declared twice"
+        out[name] = (kind(ret, False), [kind(q, True) for q in params])
+    return out
+
+
+def table_prototypes(prototypes, restypes):
+    """The same description read from the ctypes table (``_lib.PROTOTYPES`` / ``_lib._RESTYPES``)."""
+    import ctypes as C
+    from mclstexp_amd import _lib
+    scalar = {C.c_int32: "i32", C.c_int64: "i64", C.c_uint32: "u32", C.c_uint64: "u64", C.c_float: "f32", C.c_double: "f64"}
+
+    def kind(t):
+        if t is _lib.c_s:
+            return "stream"
+        if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+            return "ptr"
+        return scalar[t]
+    return {name: (kind(restypes.get(name, C.c_int)), [kind(t) for t in argtypes]) for name, argtypes in prototypes.items()}
+
+
+def prototype_mismatches(prototypes, restypes):
+    want, have = header_prototypes(), table_prototypes(prototypes, restypes)
+    bad = [f"{n}: only in {'the header' if n in want else 'PROTOTYPES'}" for n in sorted(set(want) ^ set(have))]
+    for n in sorted(set(want) & set(have)):
+        (wr, wa), (hr, ha) = want[n], have[n]
+        if wr != hr:
+            bad.append(f"{n}: returns {wr} in the header, {hr} in _RESTYPES")
+        if len(wa) != len(ha):
+            bad.append(f"{n}: {len(wa)} arguments in the header, {len(ha)} in PROTOTYPES")
+        bad += [f"{n}: argument {i} is {a} in the header, {b} in PROTOTYPES" for i, (a, b) in enumerate(zip(wa, ha)) if a != b]
+    return bad
+
+
+def test_every_prototype_matches_the_header_type_by_type():
+    """Argument count, every argument's kind and the return type of all entry points: a c_int32 typed where the header says
+    int64_t would truncate silently."""
+    from mclstexp_amd import _lib
+    want = header_prototypes()
+    assert len(want) == len(declared_symbols()) >= 180
+    kinds = {k for _, a in want.values() for k in a}
+    assert kinds == {"ptr", "i32", "i64", "u32", "u64", "f32", "f64", "stream"}           # (the parser tells them all apart)
+    assert prototype_mismatches(_lib.PROTOTYPES, _lib._RESTYPES) == []
+    # a stream is always the last argument, and only there: _lib.call appends it
+    for name, (_, args) in want.items():
+        assert "stream" not in args[:-1], name
+    assert sum(a[-1:] == ["stream"] for _, a in want.values()) == 151
+    # every value-returning entry point is listed in _RESTYPES (call() returns its result instead of checking a status)
+    assert {"mcl_abi_version", "mcl_gemm_auto_ksplit", "mcl_proj_head_ksplit", "mcl_topk_rows_max_k"} <= set(_lib._RESTYPES)
+    assert {n for n, (r, _) in want.items() if r != "i32"} <= set(_lib._RESTYPES)
+
+
+def test_prototype_check_catches_a_swapped_int_width():
+    """The check itself: c_i and c_l swapped in one row (same count, both integers) must be reported, as must a dropped
+    argument, a pointer typed as an integer and a wrong return type."""
+    import ctypes as C
+    from mclstexp_amd import _lib
+    row = _lib.PROTOTYPES["mcl_add_f32"]                       # (void*, void*, void*, int64_t n, stream)
+    assert row[3] is _lib.c_l
+
+    def mutated(name, argtypes):
+        table = dict(_lib.PROTOTYPES)
+        table[name] = argtypes
+        return prototype_mismatches(table, _lib._RESTYPES)
+    assert mutated("mcl_add_f32", row[:3] + [_lib.c_i] + row[4:]) == ["mcl_add_f32: argument 3 is i64 in the header, i32 in PROTOTYPES"]
+    bn = list(_lib.PROTOTYPES["mcl_dense_bn1_bwd"])            # (..., int32_t C, const void* x, int64_t ldx, ...)
+    assert (bn[2], bn[4]) == (_lib.c_i, _lib.c_l)
+    bn[2], bn[4] = bn[4], bn[2]
+    assert mutated("mcl_dense_bn1_bwd", bn) == ["mcl_dense_bn1_bwd: argument 2 is i32 in the header, i64 in PROTOTYPES",
+                                                "mcl_dense_bn1_bwd: argument 4 is i64 in the header, i32 in PROTOTYPES"]
+    assert mutated("mcl_add_f32", row[:-2] + row[-1:]) != []
+    assert mutated("mcl_add_f32", [_lib.c_l] + row[1:]) == ["mcl_add_f32: argument 0 is ptr in the header, i64 in PROTOTYPES"]
+    assert mutated("mcl_add_f32", row[:-1] + [_lib.c_p]) == ["mcl_add_f32: argument 4 is stream in the header, ptr in PROTOTYPES"]
+    res = dict(_lib._RESTYPES)
+    res["mcl_bn_workspace_floats"] = C.c_int32
+    assert prototype_mismatches(_lib.PROTOTYPES, res) == ["mcl_bn_workspace_floats: returns i64 in the header, i32 in _RESTYPES"]
 
 
 # ---------------------------------------------------------------- struct layouts: header == ctypes binding == INTEGRATION.md
