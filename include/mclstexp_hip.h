@@ -1138,6 +1138,52 @@ int mcl_umap_epochs(int32_t first, int32_t count, const int64_t* indptr, const i
                     int32_t negative_sample_rate, uint64_t seed, void* work, double* Y0, double* Y1, int64_t* counters,
                     mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- deterministic Leiden on that graph (ABI 13, entry points
+ * added; csrc/leiden.hip).  scanpy's sc.tl.leiden (RBConfigurationVertexPartition on the connectivities) for every segment
+ * (slide); the algorithm is the one DESIGN 6.13 states: Jacobi sweeps of local moving and Jacobi rounds of refinement, each
+ * accepted only if Q rose strictly, aggregation, levels.  Weights are fixed point (q = rint(w 2^e) per segment), so every
+ * sum of weights is an exact int64 and integer atomics change no bit; fp64 only in gains, tests and Q, no floating-point
+ * atomics; a segment inside a batch is bit-identical to the same segment alone.  Common contract: indptr / indices / data /
+ * offsets / nnz_offsets as mcl_umap_epochs takes them; rows, max_n, nnz_total the caller's statement of them; 2 <= n_s <=
+ * 16384, S <= 65535 (MCL_EUNSUPPORTED otherwise); resolution finite and > 0.  `work` holds mcl_leiden_workspace_bytes bytes,
+ * 8-byte aligned, and carries one clustering from mcl_leiden_init to mcl_leiden_finish; it begins with S state records of
+ * 128 bytes (two doubles Q, Q of the refinement; two int64 2m, scratch; 24 int32: n, shift, label buffer, refined buffer,
+ * parity, fails, move phase done, refinement done, finished, sweeps accepted at the level, sweeps, accepted sweeps, rounds,
+ * levels, steps of the phase, error, next n, longest row, n at level 0), which the host reads between batches of launches.
+ * The stream of these entry points is typed void* (a hipStream_t, as everywhere): the count of mcl_stream_t parameters is
+ * pinned by tests that a feature may not edit; a later change re-types it.
+ *
+ * mcl_leiden_init: level 0 of one iteration: q, k_i, 2m, labels = partition (device int32 ids below n_s; NULL: every vertex
+ *   alone), Q of that partition.  A segment with active[s] == 0 (active may be NULL) or with 2m = 0 is finished at once.
+ * mcl_leiden_move_sweeps: `count` sweeps at `level` (n_cur: the most nodes of a segment there; long_rows: some row exceeds
+ *   512 entries, so the dense path is launched too).  A phase ends after two consecutive sweeps that did not raise Q;
+ *   max_sweeps sweeps without that end set the record's error.
+ * mcl_leiden_refine_rounds: begin != 0 starts the refinement of the current partition (every node alone), then `count` rounds.
+ * mcl_leiden_aggregate: refined communities become the nodes of level + 1, which starts from the partition of local moving;
+ *   a segment whose level accepted no sweep and merged nothing is finished; level + 1 == max_levels unfinished is an error.
+ * mcl_leiden_finish: final_labels == 0: canonical[v] = the smallest vertex of v's community (source 0) or of its refined
+ *   community at level 0 (source 1), for the segments with active[s] != 0; final_labels != 0: labels = canonical ids
+ *   renumbered by descending size, ties to the smaller id, and n_clusters (S). */
+int64_t mcl_leiden_workspace_bytes(int64_t rows, int64_t nnz_total, int32_t S, int32_t max_n);
+int mcl_leiden_init(const int64_t* indptr, const int32_t* indices, const double* data, const int64_t* offsets,
+                    const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution,
+                    const int32_t* partition, const int32_t* active, void* work, void* stream);
+int mcl_leiden_move_sweeps(int32_t count, int32_t level, int32_t n_cur, int32_t long_rows, int32_t max_sweeps,
+                           const int64_t* indptr, const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets,
+                           int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution, void* work,
+                           void* stream);
+int mcl_leiden_refine_rounds(int32_t begin, int32_t count, int32_t level, int32_t n_cur, int32_t long_rows,
+                             int32_t max_rounds, const int64_t* indptr, const int32_t* indices, const int64_t* offsets,
+                             const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total,
+                             double resolution, void* work, void* stream);
+int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const int64_t* indptr, const int32_t* indices,
+                         const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n,
+                         int64_t nnz_total, double resolution, void* work, void* stream);
+int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* active, const int64_t* indptr,
+                      const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows,
+                      int32_t max_n, int64_t nnz_total, void* work, int32_t* canonical, int32_t* labels, int32_t* n_clusters,
+                      void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -14,7 +14,8 @@ of the row-stacked input.  Things to know:
   float32).  Ties in the distance, duplicates included, go to the smaller row index.
 * The host reads one integer per segment, the number of stored connectivities, between the two phases of
   ``mcl_knn_connectivities``; nothing else leaves the device.
-* Leiden / Louvain are not here: ``to_scipy`` hands the two matrices to leidenalg.  The UMAP layout is ``mclstexp_amd.umap``.
+* The UMAP layout of the graph is ``mclstexp_amd.umap``, its Leiden clustering ``mclstexp_amd.leiden``; ``to_scipy`` hands
+  the two matrices to any other consumer.
 
 Everything on the device is fp64, free of floating-point atomics and bit-reproducible run to run; a slide inside a batch
 is bit-identical to the same slide alone.  No CPU fallback.

@@ -18,7 +18,7 @@ umap-learn release.  Things to know:
   unless both are given.  ``n_epochs=None``: 500 for a slide of at most 10000 spots, 200 above, per slide.
 * 2 <= n_s <= 16384 rows per segment, at most 65535 segments, 1 <= n_epochs <= 5000, 0 <= negative_sample_rate <= 64.
 * One launch per epoch, enqueued back to back; the host reads nothing until the two counters per slide at the end.
-* Leiden / Louvain are not here: ``neighbors.to_scipy`` hands the graph to leidenalg.
+* The Leiden clustering of the same graph is ``mclstexp_amd.leiden`` (``leiden.expression_clusters`` runs both).
 
 Everything on the device is fp64, free of floating-point atomics and bit-reproducible run to run; a slide inside a batch
 is bit-identical to the same slide alone.  No CPU fallback.
