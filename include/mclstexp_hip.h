@@ -898,7 +898,8 @@ int mcl_corr_from_gram(const double* gram, int32_t m, double* corr, mcl_stream_t
  *   m_s x m_s with m_s = min(n_s, G): Xc^T Xc when n_s >= G ("primal"), else Xc Xc^T ("dual"); fp64 accumulation on
  *   v_mfma_f64_16x16x4_f64 in index order; full matrix, exactly symmetric.  gram_offsets[S + 1] (device int64) are element
  *   offsets, gram_offsets[s + 1] - gram_offsets[s] >= m_s^2.  max_rows = the largest n_s (sizes the grid).
- * mcl_pca_project: the top n_comps <= 64 eigenpairs of that matrix, found on the host: evec at evec_offsets[s] (device int64
+ * mcl_pca_project: the top n_comps <= 64 eigenpairs of that matrix, found on the host or by mcl_sym_eig_top (whose outputs
+ *   have this layout): evec at evec_offsets[s] (device int64
  *   element offsets) row-major (m_s, n_comps), eval[s * n_comps + c] the eigenvalues, best first.  Writes the scores
  *   z (rows, n_comps): primal Xc V, dual U sqrt(lambda) -- sklearn's PCA.fit_transform -- with each component's sign chosen
  *   so that its loading of largest magnitude (ties: the lowest column) is positive (sklearn >= 1.5's svd_flip on V);
@@ -1183,6 +1184,29 @@ int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* activ
                       const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows,
                       int32_t max_n, int64_t nnz_total, void* work, int32_t* canonical, int32_t* labels, int32_t* n_clusters,
                       void* stream);
+
+/* ---------------------------------------------------------------- leading eigenpairs of symmetric matrices (ABI 13, entry
+ * points added; csrc/eig.hip).  The k <= 64 largest eigenvalues and their eigenvectors of S dense symmetric fp64 matrices
+ * per call, by the direct method DESIGN 6.14 states: Householder tridiagonalisation, bisection on the Sturm count, block
+ * inverse iteration, back-transformation.  fp64 throughout, no floating-point atomics, no workgroup waits for another;
+ * every sum's order depends only on the slide's own m and k: a slide inside a batch is bit-identical to the same slide
+ * alone.  a: slide s is row-major m_s x m_s at a[a_offsets[s]] (device int64 element offsets, the layout mcl_pca_gram
+ * writes), exactly symmetric, both triangles; it is OVERWRITTEN (reflectors and the reduced blocks).  m[S] device int32;
+ * max_m and sum_m: the caller's statement of the largest and the sum of them.  1 <= m_s <= max_m <= 4096, 1 <= k <= 64,
+ * S <= 65535 (MCL_EUNSUPPORTED beyond), k <= max_m and S <= sum_m <= S max_m (MCL_EINVAL otherwise); k <= every m_s and
+ * the stated sum are checked on the device: a call that breaks them computes nothing and certifies NaN for every slide.
+ * evals[s * k + i]: descending.  evecs: row-major (m_s, k) at evecs[evec_offsets[s]] (device int64), the layout
+ * mcl_pca_project reads; each vector is scaled by +-1 so that its component of largest magnitude (ties: the lowest index)
+ * is positive.  cert[2 s] = max_i |T z_i - lambda_i z_i|_2 / |T|, cert[2 s + 1] = max |Z^T Z - I| of the tridiagonal
+ * problem, computed on the device.  work: mcl_sym_eig_workspace_bytes bytes, 8-byte aligned; it carries the call from one
+ * stage to the next.  stages: bit 0 the tridiagonalisation, bit 1 eigenvalues, vectors of T and the certificate, bit 2 the
+ * back-transformation and the sign; 7 runs all, and a caller that times the stages passes 1, 2, 4 in that order with the
+ * same arguments.  Enqueues about 3 max_m launches and never synchronises.  The stream is typed void* (a hipStream_t) for
+ * the reason given at mcl_leiden_init. */
+int64_t mcl_sym_eig_workspace_bytes(int32_t S, int32_t max_m, int64_t sum_m, int32_t k);
+int mcl_sym_eig_top(double* a, const int64_t* a_offsets, const int32_t* m, int32_t S, int32_t max_m, int64_t sum_m,
+                    int32_t k, int32_t stages, double* evals, double* evecs, const int64_t* evec_offsets, double* cert,
+                    void* work, void* stream);
 
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;

@@ -260,6 +260,9 @@ PROTOTYPES = {
     "mcl_leiden_refine_rounds": [c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p],
     "mcl_leiden_aggregate": [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p],
     "mcl_leiden_finish": [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p],
+    # csrc/eig.hip: the stream is a plain trailing c_p as for leiden; eig.py passes current_stream()
+    "mcl_sym_eig_workspace_bytes": [c_i, c_i, c_l, c_i],
+    "mcl_sym_eig_top": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -274,7 +277,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_gemm_workspace_floats": C.c_int64, "mcl_rowred_workspace_floats": C.c_int64,
              "mcl_proj_head_ws_floats": C.c_int64, "mcl_harmony_workspace_doubles": C.c_int64,
              "mcl_tsne_workspace_doubles": C.c_int64, "mcl_knn_workspace_bytes": C.c_int64,
-             "mcl_umap_workspace_bytes": C.c_int64, "mcl_leiden_workspace_bytes": C.c_int64}
+             "mcl_umap_workspace_bytes": C.c_int64, "mcl_leiden_workspace_bytes": C.c_int64,
+             "mcl_sym_eig_workspace_bytes": C.c_int64}
 
 
 def _signature(name: str):

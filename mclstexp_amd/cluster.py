@@ -7,7 +7,8 @@
 All slides of an evaluation run through ONE ``mcl_pca_gram`` / ``mcl_pca_project`` / ``mcl_kmeans`` /
 ``mcl_cluster_scores`` call each (csrc/cluster.hip: fp64, deterministic, a slide inside a batch is bit-identical to the same
 slide alone).  Host side on purpose: the label strings -> integer codes and the row mask (bookkeeping), and
-``numpy.linalg.eigh`` of the one small symmetric Gram matrix per slide (a device eigensolver is out of scope).  t-SNE, which
+``numpy.linalg.eigh`` of the one small symmetric Gram matrix per slide -- by default: ``solver="device"`` (``--pca_solver
+device``) hands the Gram matrices to ``mclstexp_amd.eig`` instead and they never leave the GPU.  t-SNE, which
 the reference computes and never reads, is opt-in (``tsne=True`` / ``--tsne OUT.npz``: ``mclstexp_amd.tsne`` embeds the PCA
 scores already at hand; the scores and clusters do not depend on it).  Seeding: the reference's k-means++ draws from NumPy's
 ``RandomState(0)``; that stream is NOT reproduced -- ``seed_rows`` replays given initial centres exactly, otherwise the
@@ -15,6 +16,7 @@ kernel's own k-means++ (counter-based generator) is used, best of ``n_init`` res
 the HIP library these functions raise ``RuntimeError``.
 
     python -m mclstexp_amd.cluster --pred P1.npy ... --labels L1.npy ... [--n_init N] [--json OUT] [--tsne OUT.npz]
+                                  [--pca_solver {host,device}]
 """
 from __future__ import annotations
 
@@ -25,7 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from . import _arrays
+from . import _arrays, eig
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, stack_rows, upload, write_json
 from ._lib import call
 
@@ -34,6 +36,7 @@ MAX_DIM = 64         # D <= 64 and K <= 64 (csrc/cluster.hip)
 MAX_ROWS = 50000     # per segment: the pair counts of the ARI stay inside int64
 MAX_LABEL = 1024     # label values in [0, 1024)
 MAX_TABLE = 12288    # distinct(a) * distinct(b) per segment
+SOLVERS = ("host", "device")   # of the PCA's symmetric eigenproblem: numpy.linalg.eigh / mclstexp_amd.eig
 
 
 def validate_offsets(offsets: Optional[Sequence[int]], rows: int, min_rows: int = 1) -> np.ndarray:
@@ -57,10 +60,16 @@ def _labels_i32(v: ArrayLike, name: str, dev: torch.device) -> Tensor:
 
 
 # ------------------------------------------------------------------------------------------------------------ PCA
-def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: int = N_COMPS) -> Dict[str, object]:
+def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: int = N_COMPS,
+               solver: str = "host") -> Dict[str, object]:
     """PCA scores of every segment of the row-stacked (spots, genes) matrix ``x`` (fp32 / fp64), as sklearn's
     ``PCA(n_comps, svd_solver="arpack").fit_transform`` gives them (scanpy's ``pp.pca`` default): device ``scores``
-    (rows, n_comps) fp64 and ``sign`` (S, n_comps); host ``explained_variance`` (S, n_comps) = eigenvalue / (n_s - 1)."""
+    (rows, n_comps) fp64 and ``sign`` (S, n_comps); host ``explained_variance`` (S, n_comps) = eigenvalue / (n_s - 1).
+    ``solver``: ``"host"`` copies the Gram matrices to the host for ``numpy.linalg.eigh``; ``"device"`` solves for the
+    leading eigenpairs on the GPU (``mclstexp_amd.eig``, min(spots, genes) <= 4096 in every segment): the Gram matrices
+    never cross to the host, only the certificate and the (S, n_comps) eigenvalues are read back."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     if not isinstance(x, Tensor) and np.asarray(x).ndim != 2:
         raise ValueError(f"x: expected a 2-D (spots, genes) array, got shape {np.asarray(x).shape}")
     rows, G = int(x.shape[0]), int(x.shape[1])
@@ -73,6 +82,9 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     if n_comps >= int(m.min()):
         raise ValueError(f"n_comps = {n_comps} needs more than {n_comps} spots and genes in every segment "
                          f"(smallest min(spots, genes) = {int(m.min())})")
+    if solver == "device" and int(m.max()) > eig.MAX_M:
+        raise ValueError(f"solver=\"device\" handles min(spots, genes) <= {eig.MAX_M} per segment, got {int(m.max())}; "
+                         f"use solver=\"host\"")
     dev = device("cluster")
     xd = matrix(x, "x", dev, FLOAT_CODE, torch.float64)
     S = off.size - 1
@@ -83,32 +95,42 @@ def pca_device(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: i
     gram = e((int(goff[-1]),), torch.float64)
     max_rows = int(seg.max())
     call("mcl_pca_gram", xd, xd.stride(0), FLOAT_CODE[xd.dtype], off_d, S, G, max_rows, goff_d, mean, gram)
-    gram_h = gram.cpu().numpy()                      # the one synchronisation of the pipeline
-    evec = np.empty((int(eoff[-1]),), dtype=np.float64)
-    evals = np.empty((S, n_comps), dtype=np.float64)
-    for s in range(S):
-        ms = int(m[s])
-        w, v = np.linalg.eigh(gram_h[goff[s]:goff[s + 1]].reshape(ms, ms))      # ascending
-        evals[s] = w[::-1][:n_comps]
-        evec[eoff[s]:eoff[s + 1]] = np.ascontiguousarray(v[:, ::-1][:, :n_comps]).reshape(-1)
-    evec_d, eval_d, eoff_d = upload(evec, dev), upload(evals, dev), upload(eoff, dev)
+    if solver == "device":
+        res = eig.solve(gram, goff, m, n_comps, evec_offsets=eoff, a_offsets_d=goff_d)      # gram is overwritten
+        evec_d, eval_d, eoff_d = res["vectors_flat"], res["values"], res["evec_offsets"]
+    else:
+        gram_h = gram.cpu().numpy()                      # the one synchronisation of the pipeline
+        evec = np.empty((int(eoff[-1]),), dtype=np.float64)
+        evals = np.empty((S, n_comps), dtype=np.float64)
+        for s in range(S):
+            ms = int(m[s])
+            w, v = np.linalg.eigh(gram_h[goff[s]:goff[s + 1]].reshape(ms, ms))      # ascending
+            evals[s] = w[::-1][:n_comps]
+            evec[eoff[s]:eoff[s + 1]] = np.ascontiguousarray(v[:, ::-1][:, :n_comps]).reshape(-1)
+        evec_d, eval_d, eoff_d = upload(evec, dev), upload(evals, dev), upload(eoff, dev)
     loadings = e((S * G * n_comps,), torch.float64)
     sign, z = e((S, n_comps), torch.float64), e((rows, n_comps), torch.float64)
     call("mcl_pca_project", xd, xd.stride(0), FLOAT_CODE[xd.dtype], off_d, S,
          G, max_rows, n_comps, mean, evec_d, eoff_d, eval_d, loadings, sign, z)
+    if solver == "device":
+        eig.check_certificate(res["certificate"].cpu().numpy(), res["sizes"])     # read back after everything is enqueued
+        evals = eval_d.cpu().numpy()
     return {"scores": z, "sign": sign, "explained_variance": np.maximum(evals, 0.0) / (seg[:, None] - 1.0),
             "offsets": off}
 
 
-def pca_scores(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: int = N_COMPS) -> Tensor:
+def pca_scores(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_comps: int = N_COMPS,
+               solver: str = "host") -> Tensor:
     """Device (rows, n_comps) fp64 PCA scores of every segment of ``x`` (see ``pca_device``)."""
-    return pca_device(x, offsets, n_comps)["scores"]
+    return pca_device(x, offsets, n_comps, solver)["scores"]
 
 
-def pca_scores_slides(xs: Sequence[ArrayLike], n_comps: int = N_COMPS) -> List[Tensor]:
+def pca_scores_slides(xs: Sequence[ArrayLike], n_comps: int = N_COMPS, solver: str = "host") -> List[Tensor]:
     """One (spots_i, n_comps) device score matrix per slide, all slides in one gram and one project call."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     x, off = stack_rows(xs, "xs", device("cluster"))
-    z = pca_scores(x, off, n_comps)
+    z = pca_scores(x, off, n_comps, solver)
     return [z[off[i]:off[i + 1]] for i in range(len(xs))]
 
 
@@ -258,14 +280,17 @@ def _take_rows(x: ArrayLike, idx: np.ndarray, dev: torch.device) -> ArrayLike:
 
 def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undetermined="undetermined",
                    n_comps: int = N_COMPS, seed_rows=None, n_init: int = 1, seed: int = 0, tol: float = 1e-4,
-                   max_iter: int = 300, segment_base: int = 0, tsne: Union[bool, dict] = False) -> Dict[str, object]:
+                   max_iter: int = 300, segment_base: int = 0, tsne: Union[bool, dict] = False,
+                   solver: str = "host") -> Dict[str, object]:
     """cluster() for every slide of an evaluation in ONE gram / ONE project / ONE kmeans / ONE scores call.
     ``preds[i]``: (spots_i, genes) predicted expression, ``labels[i]``: (spots_i,) annotations.  Returns ``slides``: per
     slide ``p`` (cluster index per kept spot, int32), ``ari``, ``nmi`` (rounded to 3 decimals as the reference does),
     ``ari_raw``, ``nmi_raw``, ``k``, ``inertia``, ``n_iter``, ``restart``; and ``ari``, ``nmi``: the means over slides of
     the rounded values.  ``tsne`` (True, or a dict of ``mclstexp_amd.tsne.tsne`` arguments): every slide also gets ``tsne``,
     the (kept spots, 2) exact t-SNE embedding of its PCA scores (the reference's ``sc.tl.tsne``), as a numpy array;
-    everything else is what ``tsne=False`` gives."""
+    everything else is what ``tsne=False`` gives.  ``solver``: the PCA's eigensolver (see ``pca_device``)."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
     if len(preds) != len(labels) or not len(preds):
         raise ValueError(f"need one label vector per prediction and >= 1 slide; got {len(preds)} and {len(labels)}")
     enc = []
@@ -279,7 +304,7 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
     dev = device("cluster")
     x, off = stack_rows([_take_rows(p, e[0], dev) for p, e in zip(preds, enc)], "preds", dev)
     _k_per_segment(ks, np.diff(off))
-    z = pca_scores(x, off, n_comps)
+    z = pca_scores(x, off, n_comps, solver)
     km = kmeans(z, ks, off, seed_rows=seed_rows, n_init=n_init, seed=seed, tol=tol, max_iter=max_iter,
                 segment_base=segment_base)
     truth = upload(np.concatenate([e[1] for e in enc]), dev)
@@ -299,13 +324,14 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
 
 
 def cluster(pred: ArrayLike, label: Sequence, undetermined="undetermined", n_comps: int = N_COMPS, seed_rows=None,
-            n_init: int = 1, seed: int = 0, tsne: Union[bool, dict] = False) -> tuple:
+            n_init: int = 1, seed: int = 0, tsne: Union[bool, dict] = False, solver: str = "host") -> tuple:
     """The reference's ``cluster(adata, label)`` -> ``(p, ari, nmi)``: ``p`` the cluster index of every kept spot,
     ``ari`` / ``nmi`` rounded to 3 decimals.  ``seed_rows`` (n_restarts, k) or (k,): initial centres as rows of the kept
-    spots.  ``tsne`` (see ``cluster_slides``): ``(p, ari, nmi, embedding)``."""
+    spots.  ``tsne`` (see ``cluster_slides``): ``(p, ari, nmi, embedding)``.  ``solver``: see ``pca_device``."""
     if seed_rows is not None:
         seed_rows = [np.asarray(seed_rows)]
-    s = cluster_slides([pred], [label], undetermined, n_comps, seed_rows, n_init, seed, tsne=tsne)["slides"][0]
+    s = cluster_slides([pred], [label], undetermined, n_comps, seed_rows, n_init, seed, tsne=tsne,
+                       solver=solver)["slides"][0]
     if "tsne" in s:
         return s["p"], s["ari"], s["nmi"], s["tsne"]
     return s["p"], s["ari"], s["nmi"]
@@ -325,6 +351,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
     p.add_argument("--json", default=None, help="also write per-slide and mean scores to this file")
     p.add_argument("--tsne", default=None, metavar="OUT.npz",
                    help="also embed every slide's PCA scores by exact t-SNE and write slide_<i> arrays (kept spots, 2)")
+    p.add_argument("--pca_solver", choices=SOLVERS, default="host",
+                   help="eigensolver of the PCA: numpy.linalg.eigh on the host (default) or mclstexp_amd.eig on the GPU")
     a = p.parse_args(argv)
     if len(a.pred) != len(a.labels):
         p.error(f"{len(a.pred)} --pred files but {len(a.labels)} --labels files")
@@ -342,7 +370,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     a = parse_args(argv)
     preds = [np.load(f) for f in a.pred]
     labels = [np.load(f, allow_pickle=False) for f in a.labels]
-    res = cluster_slides(preds, labels, a.undetermined, a.n_comps, None, a.n_init, a.seed, tsne=a.tsne is not None)
+    res = cluster_slides(preds, labels, a.undetermined, a.n_comps, None, a.n_init, a.seed, tsne=a.tsne is not None,
+                         solver=a.pca_solver)
     print(format_report(res))
     if a.tsne:
         np.savez(a.tsne, **{f"slide_{i}": s.pop("tsne") for i, s in enumerate(res["slides"])})

@@ -6,7 +6,8 @@
 //   mcl_pca_gram        pca_mean_kernel (column means) + pca_gram_kernel: the centred Gram matrix in its smaller form,
 //                       Xc^T Xc (G x G) when n_s >= G ("primal"), else Xc Xc^T (n_s x n_s) ("dual"), on
 //                       v_mfma_f64_16x16x4_f64; the lower triangle of 64x64 blocks is computed and mirrored.
-//   (host)              numpy.linalg.eigh of that one symmetric matrix per segment.
+//   (host, or device)   the leading eigenpairs of that one symmetric matrix per segment: numpy.linalg.eigh on the host by
+//                       default, mcl_sym_eig_top (csrc/eig.hip) on request -- then the Gram matrices stay on the device.
 //   mcl_pca_project     pca_loadings_kernel + pca_sign_kernel + pca_scores_kernel: the scores Xc V (primal) or U sqrt(lambda)
 //                       (dual), each component's sign fixed so that its loading of largest magnitude is positive.
 //   mcl_kmeans          kmeans_kernel, grid (restart, segment): one workgroup runs one whole Lloyd problem (seeding, the

@@ -268,8 +268,9 @@ def cluster(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_neighbors: 
 def expression_clusters(expr: ArrayLike, batch_idx=None, preprocess: bool = True, normalize_and_log: bool = True,
                         n_top_genes: int = neighbors.N_TOP_GENES, n_pcs: int = neighbors.N_PCS,
                         n_neighbors: int = neighbors.N_NEIGHBORS, layout: bool = True, umap_kw: Optional[Dict[str, object]] = None,
-                        **kw) -> Dict[str, object]:
-    """``visualize_umap_clusters`` on one (spots, genes) matrix: ``neighbors.expression_graph`` (its arguments), with
+                        pca_solver: str = "host", **kw) -> Dict[str, object]:
+    """``visualize_umap_clusters`` on one (spots, genes) matrix: ``neighbors.expression_graph`` (its arguments,
+    ``pca_solver`` among them), with
     ``layout`` the UMAP layout started from the PCA scores (``umap_kw``: keywords of ``umap.layout``), and ``leiden`` (its
     keywords) on the same graph.  Returns the clustering's dict plus ``graph`` and ``embedding`` (None without ``layout``)."""
     _check_keywords(kw)
@@ -278,7 +279,8 @@ def expression_clusters(expr: ArrayLike, batch_idx=None, preprocess: bool = True
         if n_pcs < 2:
             raise ValueError(f"n_pcs must be at least 2 for the PCA start of the layout, got {n_pcs}")
         umap._check_keywords(umap_kw.get("init", "pca"), {k: v for k, v in umap_kw.items() if k != "init"})
-    graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors)
+    graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors,
+                                       pca_solver)
     embedding = None
     if layout:
         init = umap_kw.pop("init", "pca")

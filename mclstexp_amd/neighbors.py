@@ -244,14 +244,18 @@ def to_scipy(res: Dict[str, object], segment: int = 0):
 
 # ---------------------------------------------------------------------------------------------------- the notebook
 def expression_graph(expr: ArrayLike, batch_idx=None, preprocess: bool = True, normalize_and_log: bool = True,
-                     n_top_genes: int = N_TOP_GENES, n_pcs: int = N_PCS, n_neighbors: int = N_NEIGHBORS) -> Dict[str, object]:
+                     n_top_genes: int = N_TOP_GENES, n_pcs: int = N_PCS, n_neighbors: int = N_NEIGHBORS,
+                     pca_solver: str = "host") -> Dict[str, object]:
     """``visualize_umap_clusters`` up to and including ``sc.pp.neighbors`` on one (spots, genes) matrix.
     ``preprocess=True``: the flags of ``preprocess.gene_stats`` (normalize_total, log1p, highly_variable_genes), the
     notebook's ``n_top_genes:  N`` line, then the PCA (``cluster.pca_device``, ``n_pcs`` components) of the flagged
     columns as ``preprocess.expression_matrices`` log-normalises them (log10(c / rowsum 1e4 + 1), the row sum over the
     flagged genes: this library's expression matrix, not scanpy's ln(c / size x median + 1) over all genes), then the
     graph.  ``preprocess=False``: the PCA of the matrix as given.  Returns ``neighbors``' dict plus ``scores`` (spots,
-    n_pcs), ``highly_variable`` ((genes,) bool on the device, or None) and ``batch_idx`` as it was passed."""
+    n_pcs), ``highly_variable`` ((genes,) bool on the device, or None) and ``batch_idx`` as it was passed.
+    ``pca_solver``: the PCA's eigensolver, ``"host"`` or ``"device"`` (``cluster.pca_device``'s ``solver``)."""
+    if pca_solver not in cluster.SOLVERS:
+        raise ValueError(f"pca_solver must be one of {cluster.SOLVERS}, got {pca_solver!r}")
     if preprocess and not normalize_and_log:
         raise ValueError("preprocess=True with normalize_and_log=False is not available: preprocess.gene_stats normalises "
                          "and takes the logarithm by construction (pass counts, or preprocess=False for a ready matrix)")
@@ -266,7 +270,7 @@ def expression_graph(expr: ArrayLike, batch_idx=None, preprocess: bool = True, n
         genes = np.flatnonzero(hv.cpu().numpy())
         print("n_top_genes: ", int(genes.size))
         x = _pre.expression_matrices([counts], None, genes)[0].T
-    scores = cluster.pca_device(x, None, n_pcs)["scores"]
+    scores = cluster.pca_device(x, None, n_pcs, pca_solver)["scores"]
     res = neighbors(scores, None, n_neighbors)
     res.update(scores=scores, highly_variable=hv, batch_idx=batch_idx)
     return res

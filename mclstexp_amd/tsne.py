@@ -284,10 +284,12 @@ def update(Y: ArrayLike, grad: ArrayLike, upd: ArrayLike, gains: ArrayLike, offs
 def tsne(x: ArrayLike, offsets: Optional[Sequence[int]] = None, perplexity: float = 30.0,
          early_exaggeration: float = 12.0, learning_rate: Union[str, float] = "auto", n_iter: int = 1000,
          init: Union[str, ArrayLike] = "pca", random_state: int = 0,
-         float32_distances: bool = False) -> Dict[str, object]:
+         float32_distances: bool = False, pca_solver: str = "host") -> Dict[str, object]:
     """Exact t-SNE of every segment of the row-stacked (rows, D <= 64) matrix ``x`` (see the module docstring).  Returns
     device ``embedding`` (rows, 2) fp64 and ``beta`` (rows,), host ``kl_divergence`` (S,), ``n_iter`` (S,) and
-    ``offsets``."""
+    ``offsets``.  ``pca_solver``: the eigensolver of the ``"pca"`` start (``cluster.pca_device``'s ``solver``)."""
+    if pca_solver not in cluster.SOLVERS:
+        raise ValueError(f"pca_solver must be one of {cluster.SOLVERS}, got {pca_solver!r}")
     off, seg, D = _check_x(x, offsets, perplexity)
     rows, S = int(off[-1]), seg.size
     n_iter = int(n_iter)
@@ -311,7 +313,7 @@ def tsne(x: ArrayLike, offsets: Optional[Sequence[int]] = None, perplexity: floa
         y0 = init
     dev = device("tsne")
     if y0 is None:
-        y0 = scale_pca_init(cluster.pca_device(x, off, 2)["scores"].cpu().numpy(), off)
+        y0 = scale_pca_init(cluster.pca_device(x, off, 2, pca_solver)["scores"].cpu().numpy(), off)
     aff = joint_probabilities(x, off, perplexity, float32_distances)
     plan, P = aff["_plan"], aff["P"]
     e = empty(dev)
@@ -339,12 +341,14 @@ def tsne(x: ArrayLike, offsets: Optional[Sequence[int]] = None, perplexity: floa
             "offsets": off}
 
 
-def embed_slides(matrices: Sequence[ArrayLike], n_pcs: int = cluster.N_COMPS, **kw) -> Dict[str, object]:
-    """The reference's sequence for every slide in one call each: ``cluster.pca_scores_slides`` (``n_pcs`` components),
-    then ``tsne`` of the scores.  Returns ``tsne``'s dict plus ``slides``: the (spots_i, 2) device views per slide."""
-    parts = cluster.pca_scores_slides(matrices, n_pcs)
+def embed_slides(matrices: Sequence[ArrayLike], n_pcs: int = cluster.N_COMPS, pca_solver: str = "host",
+                 **kw) -> Dict[str, object]:
+    """The reference's sequence for every slide in one call each: ``cluster.pca_scores_slides`` (``n_pcs`` components,
+    eigensolver ``pca_solver``), then ``tsne`` of the scores (whose ``"pca"`` start uses the same solver).  Returns
+    ``tsne``'s dict plus ``slides``: the (spots_i, 2) device views per slide."""
+    parts = cluster.pca_scores_slides(matrices, n_pcs, pca_solver)
     z, off = stack_rows(parts, "scores", device("tsne"))
-    res = tsne(z, off, **kw)
+    res = tsne(z, off, pca_solver=pca_solver, **kw)
     res["slides"] = [res["embedding"][off[i]:off[i + 1]] for i in range(len(parts))]
     return res
 

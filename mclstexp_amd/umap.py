@@ -229,15 +229,16 @@ def umap(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_neighbors: int
 
 def expression_umap(expr: ArrayLike, batch_idx=None, preprocess: bool = True, normalize_and_log: bool = True,
                     n_top_genes: int = neighbors.N_TOP_GENES, n_pcs: int = neighbors.N_PCS,
-                    n_neighbors: int = neighbors.N_NEIGHBORS, **kw) -> Dict[str, object]:
+                    n_neighbors: int = neighbors.N_NEIGHBORS, pca_solver: str = "host", **kw) -> Dict[str, object]:
     """``visualize_umap_clusters`` up to and including ``sc.tl.umap`` on one (spots, genes) matrix:
-    ``neighbors.expression_graph`` (its arguments), then ``layout`` (its keywords) started from the PCA scores.  Needs
+    ``neighbors.expression_graph`` (its arguments, ``pca_solver`` among them), then ``layout`` (its keywords) started from the PCA scores.  Needs
     ``n_pcs >= 2``.  Returns the layout's dict plus ``graph``, the dict of ``expression_graph``."""
     if n_pcs < 2:
         raise ValueError(f"n_pcs must be at least 2 for the PCA start, got {n_pcs}")
     init = kw.pop("init", "pca")
     _check_keywords(init, kw)
-    graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors)
+    graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors,
+                                       pca_solver)
     res = layout(graph, init, x=graph["scores"], **kw)
     res["graph"] = graph
     return res
