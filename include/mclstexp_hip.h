@@ -1208,6 +1208,52 @@ int mcl_sym_eig_top(double* a, const int64_t* a_offsets, const int32_t* m, int32
                     int32_t k, int32_t stages, double* evals, double* evecs, const int64_t* evec_offsets, double* cert,
                     void* work, void* stream);
 
+/* ---------------------------------------------------------------- marker genes of spot groups (ABI 13, entry points added;
+ * csrc/markers.hip).  scanpy's sc.tl.rank_genes_groups(adata, groupby, reference="rest") for every slide of an evaluation
+ * per call: Wilcoxon rank-sum and Welch t (DESIGN 6.15 states the arithmetic).  Common contract: x row-stacked (rows, G),
+ * dtype 0 = fp32 / 1 = fp64, row stride ld >= G; offsets: S + 1 device int64 slide boundaries; labels: rows device int32,
+ * within slide s in [0, k[s]) or -1 (the row is dropped from everything); k: S device int32.  max_n, kmax, groups_total:
+ * the caller's statement of the largest slide, the largest k and sum k.  2 <= n_s <= max_n <= 16384, 1 <= k[s] <= kmax <=
+ * 255, G <= 16384, S <= 65535, S <= groups_total <= S kmax: anything else is MCL_EINVAL before a launch; the device checks
+ * offsets, k and labels against the statements, and a slide that breaks them is skipped and counted in status.  Group g of
+ * slide s is group row sum_{s' < s} k[s'] + g of every (groups_total, G) output.  work: mcl_marker_workspace_bytes bytes,
+ * 8-byte aligned; mcl_marker_stats fills it and the three other calls read it, so they follow it on the same stream with
+ * the same S, rows, G, kmax, groups_total.  fp64 and exact int64, no floating-point atomics, deterministic; a slide inside
+ * a batch is bit-identical to the same slide alone.  The stream is typed void* (a hipStream_t) for the reason given at
+ * mcl_leiden_init.
+ *
+ * mcl_marker_stats: group_sizes (groups_total), n_valid (S): rows with a label >= 0; per (group row, gene): mean and
+ *   variance (ddof 1, NaN below two rows) of the group and of the rest, the fraction and the count of x != 0 of both;
+ *   status[2 s] = non-finite values among the kept rows of slide s, status[2 s + 1] = labels outside [-1, k[s]) plus one if
+ *   the slide's offsets or k break the statements.
+ * mcl_marker_rank_sums: rank_sums2 (groups_total, G) = sum over the group's rows of twice the tie-averaged rank among the
+ *   slide's kept rows (-0.0 ties with +0.0); tie_terms (S, G) = sum over tie runs of t^3 - t.  Exact int64.
+ * mcl_marker_test: method 0 Wilcoxon (tie_correct != 0: the variance is scaled by 1 - T / (N^3 - N)), 1 Welch t, 2 Welch t
+ *   with the rest's variance over the group's size; scores, pvals, neglog10_pvals (log space: finite where pvals is 0),
+ *   logfoldchanges = log2((expm1(mean) + 1e-9) / (expm1(mean_rest) + 1e-9)).  rank_sums2 / tie_terms may be NULL for 1, 2.
+ * mcl_marker_rank_adjust: pvals_adj (groups_total, G) = Benjamini-Hochberg over the G genes of a group row, in gene order;
+ *   names (groups_total, n_genes) = the genes by descending score (rankby_abs != 0: |score|), equal scores by gene index,
+ *   and the five columns gathered in that order. */
+int64_t mcl_marker_workspace_bytes(int64_t rows, int64_t groups_total, int32_t S, int32_t G);
+int mcl_marker_stats(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, const int32_t* labels,
+                     const int32_t* k, int32_t S, int64_t rows, int32_t G, int32_t max_n, int32_t kmax,
+                     int64_t groups_total, void* work, int32_t* group_sizes, int32_t* n_valid, double* mean_g,
+                     double* var_g, double* mean_r, double* var_r, double* pts_g, double* pts_r, int32_t* nnz_g,
+                     int32_t* nnz_r, int32_t* status, void* stream);
+int mcl_marker_rank_sums(const void* x, int64_t ld, int32_t dtype, const int32_t* labels, int32_t S, int64_t rows,
+                         int32_t G, int32_t max_n, int32_t kmax, int64_t groups_total, void* work, int64_t* rank_sums2,
+                         int64_t* tie_terms, void* stream);
+int mcl_marker_test(int32_t method, int32_t tie_correct, int32_t S, int64_t rows, int32_t G, int32_t kmax,
+                    int64_t groups_total, const void* work, const int32_t* group_sizes, const double* mean_g,
+                    const double* var_g, const double* mean_r, const double* var_r, const int64_t* rank_sums2,
+                    const int64_t* tie_terms, double* scores, double* pvals, double* neglog10_pvals,
+                    double* logfoldchanges, void* stream);
+int mcl_marker_rank_adjust(int32_t S, int64_t rows, int32_t G, int32_t kmax, int64_t groups_total, int32_t n_genes,
+                           int32_t rankby_abs, void* work, const double* scores, const double* pvals,
+                           const double* neglog10_pvals, const double* logfoldchanges, double* pvals_adj, int64_t* names,
+                           double* top_scores, double* top_pvals, double* top_pvals_adj, double* top_neglog10_pvals,
+                           double* top_logfoldchanges, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -263,6 +263,14 @@ PROTOTYPES = {
     # csrc/eig.hip: the stream is a plain trailing c_p as for leiden; eig.py passes current_stream()
     "mcl_sym_eig_workspace_bytes": [c_i, c_i, c_l, c_i],
     "mcl_sym_eig_top": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    # csrc/markers.hip: the stream is a plain trailing c_p as for leiden; markers.py passes current_stream()
+    "mcl_marker_workspace_bytes": [c_l, c_l, c_i, c_i],
+    "mcl_marker_stats": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                         c_p, c_p, c_p, c_p, c_p],
+    "mcl_marker_rank_sums": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p],
+    "mcl_marker_test": [c_i, c_i, c_i, c_l, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_marker_rank_adjust": [c_i, c_l, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                               c_p],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -278,7 +286,7 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_proj_head_ws_floats": C.c_int64, "mcl_harmony_workspace_doubles": C.c_int64,
              "mcl_tsne_workspace_doubles": C.c_int64, "mcl_knn_workspace_bytes": C.c_int64,
              "mcl_umap_workspace_bytes": C.c_int64, "mcl_leiden_workspace_bytes": C.c_int64,
-             "mcl_sym_eig_workspace_bytes": C.c_int64}
+             "mcl_sym_eig_workspace_bytes": C.c_int64, "mcl_marker_workspace_bytes": C.c_int64}
 
 
 def _signature(name: str):

@@ -16,45 +16,13 @@
 //   gene_order_kernel      gridded over genes: the exact descending rank of every gene by counting against all G means
 //                          (staged through LDS in tiles), ties to the lower gene index, NaN means last.
 #include "common.h"
+#include "betacf.h"   // log_betacf_sym, CF_MAX_ITER
 
 namespace {
 
 constexpr int PV_THREADS = 256;
 constexpr int RANK_THREADS = 256;
-constexpr int CF_MAX_ITER = 1000;   // 7 - 80 trips at n <= 4900; the trip count grows like sqrt(a)
 constexpr int MAX_GENES = 1048576;
-
-// log of the continued fraction of I_x(a, a), x <= 1/2 (modified Lentz); NaN if it has not converged in CF_MAX_ITER trips
-__device__ double log_betacf_sym(double a, double x) {
-  const double tiny = 1e-300;
-  const double tol = 4.440892098500626e-16;  // 2 ulp of 1
-  const double qab = 2.0 * a, qap = a + 1.0, qam = a - 1.0;
-  double c = 1.0;
-  double d = 1.0 - qab * x / qap;
-  if (fabs(d) < tiny) d = tiny;
-  d = 1.0 / d;
-  double h = d;
-  for (int m = 1; m <= CF_MAX_ITER; ++m) {
-    const double dm = (double)m, m2 = 2.0 * dm;
-    double aa = dm * (a - dm) * x / ((qam + m2) * (a + m2));
-    d = 1.0 + aa * d;
-    if (fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    h *= d * c;
-    aa = -(a + dm) * (qab + dm) * x / ((a + m2) * (qap + m2));
-    d = 1.0 + aa * d;
-    if (fabs(d) < tiny) d = tiny;
-    c = 1.0 + aa / c;
-    if (fabs(c) < tiny) c = tiny;
-    d = 1.0 / d;
-    const double del = d * c;
-    h *= del;
-    if (fabs(del - 1.0) <= tol) return log(h);
-  }
-  return NAN;
-}
 
 __global__ __launch_bounds__(PV_THREADS) void pearson_pvalue_kernel(const double* __restrict__ r_all,
                                                                     const long long* __restrict__ offsets, int G,
