@@ -1254,6 +1254,54 @@ int mcl_marker_rank_adjust(int32_t S, int64_t rows, int32_t G, int32_t kmax, int
                            double* top_scores, double* top_pvals, double* top_pvals_adj, double* top_neglog10_pvals,
                            double* top_logfoldchanges, void* stream);
 
+/* ---------------------------------------------------------------- spatial autocorrelation (csrc/spatial.hip)
+ * Moran's I and Geary's C of every gene on the spot lattice graph of every slide, the analytic moments under normality and
+ * a permutation test.  Slide s owns rows offsets[s] .. offsets[s + 1] (device int64, S + 1 entries) of every row-stacked
+ * array; S, rows and max_n are the caller's statement of them: 2 <= n_s <= max_n <= 16384, 1 <= k <= 64, G <= 16384,
+ * n_perms <= 65535, S <= 65535 (mcl_spatial_moments: 32767): anything else is MCL_EINVAL before a launch; a slide whose
+ * offsets break the statements is skipped and counted in status.  The graph is a fixed-width list: nbr (rows, k) int32
+ * segment-local, w (rows, k) fp64 (0 = a pruned slot), deg (rows,) = kept slots; consts (S, 3) = S0, S1, S2.  fp64, every
+ * sum over the rows of a slide in one fixed order that depends on n alone, no floating-point atomics, deterministic; a slide
+ * inside a batch is bit-identical to the same slide alone.  The stream is typed void* (a hipStream_t) for the reason given at
+ * mcl_leiden_init.
+ *
+ * mcl_spatial_workspace_bytes: hist_slots = k + 1 and n_perms = 0 for mcl_spatial_lattice; hist_slots = 0 for the
+ *   permutation table, which is uint16 (n_perms, n_s) per slide at element offset n_perms * offsets[s].
+ * mcl_spatial_columns: the gene columns a workgroup of mcl_spatial_stats takes for a slide of n rows (1 .. 6).
+ * mcl_spatial_lattice: given = 0: knn_indices / knn_distances are the (rows, k + 1) lists of mcl_knn_exact over the
+ *   coordinates (position 0 the row itself); needs n_s >= k + 1; prune 0 keeps all k, 1 keeps d <= mean + population std of
+ *   the row's k distances, 2 keeps d <= 2; kept edges weigh 1, or 1 / deg with row_standardise.  given != 0: nbr and w are
+ *   inputs and are validated; deg and consts are outputs either way.  status (S, 6): offsets broken, indices out of range,
+ *   weights negative or non-finite, neighbours listed twice, rows that are not binary, rows that are not row-standardised;
+ *   consts are NaN for a slide that is refused.
+ * mcl_spatial_permutations: fills the table: permutation p of a slide of n rows is a function of (seed, p, n) alone.
+ * mcl_spatial_stats: stat (2, S, n_perms, G): Moran's I, then Geary's C, of x (rows, G; dtype 0 fp32, 1 fp64; row stride
+ *   ld) with row i taking the value of row table[p][i].  table = NULL: the identity, n_perms = 1, and mean / den (S, G) are
+ *   written: the observed statistic, from the same code.  column_mask: bit c set = launch the c-column kernel (the caller
+ *   sets the bits mcl_spatial_columns gives for its slides).  status (S,): non-finite values of x (accumulated).
+ * mcl_spatial_moments: z, p (two_tailed != 0: both tails) and -log10 p (log space) under normality, and the
+ *   Benjamini-Hochberg adjustment over the G genes of a (statistic, slide); all (2, S, G); prank / scratch: (2, S, G) scratch.
+ * mcl_spatial_perm_summary: per (statistic, slide, gene) over the n_perms sims: count = #(sims >= stat) folded to the smaller
+ *   tail, pval_sim = (count + 1) / (n_perms + 1), mean and population variance summed over p ascending, and the normal p of
+ *   (stat - mean) / sqrt(var). */
+int64_t mcl_spatial_workspace_bytes(int64_t rows, int32_t hist_slots, int32_t n_perms);
+int32_t mcl_spatial_columns(int32_t n);
+int mcl_spatial_lattice(const int32_t* knn_indices, const double* knn_distances, const int64_t* offsets, int32_t S,
+                        int64_t rows, int32_t max_n, int32_t k, int32_t prune, int32_t row_standardise, int32_t given,
+                        void* work, int32_t* nbr, double* w, int32_t* deg, double* consts, int32_t* status, void* stream);
+int mcl_spatial_permutations(const int64_t* offsets, int32_t S, int64_t rows, int32_t max_n, int32_t n_perms,
+                             uint64_t seed, void* work, void* stream);
+int mcl_spatial_stats(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G,
+                      int32_t max_n, int32_t k, int32_t column_mask, const int32_t* nbr, const double* w,
+                      const double* consts, const void* table, int32_t n_perms, double* mean, double* den, double* stat,
+                      int32_t* status, void* stream);
+int mcl_spatial_moments(const int64_t* offsets, int32_t S, int64_t rows, int32_t G, int32_t max_n, const double* consts,
+                        const double* stat, int32_t two_tailed, int32_t* prank, double* scratch, double* z_norm,
+                        double* pval_norm, double* neglog10_pval_norm, double* pval_norm_adj, void* stream);
+int mcl_spatial_perm_summary(int32_t S, int32_t G, int32_t n_perms, const double* stat, const double* sims,
+                             int32_t two_tailed, int32_t* count, double* pval_sim, double* pval_z_sim, double* mean_sim,
+                             double* var_sim, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -271,6 +271,14 @@ PROTOTYPES = {
     "mcl_marker_test": [c_i, c_i, c_i, c_l, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_marker_rank_adjust": [c_i, c_l, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
                                c_p],
+    # csrc/spatial.hip: the stream is a plain trailing c_p as for leiden; spatial.py passes current_stream()
+    "mcl_spatial_workspace_bytes": [c_l, c_i, c_i],
+    "mcl_spatial_columns": [c_i],
+    "mcl_spatial_lattice": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_spatial_permutations": [c_p, c_i, c_l, c_i, c_i, C.c_uint64, c_p, c_p],
+    "mcl_spatial_stats": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    "mcl_spatial_moments": [c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_spatial_perm_summary": [c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -286,7 +294,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_proj_head_ws_floats": C.c_int64, "mcl_harmony_workspace_doubles": C.c_int64,
              "mcl_tsne_workspace_doubles": C.c_int64, "mcl_knn_workspace_bytes": C.c_int64,
              "mcl_umap_workspace_bytes": C.c_int64, "mcl_leiden_workspace_bytes": C.c_int64,
-             "mcl_sym_eig_workspace_bytes": C.c_int64, "mcl_marker_workspace_bytes": C.c_int64}
+             "mcl_sym_eig_workspace_bytes": C.c_int64, "mcl_marker_workspace_bytes": C.c_int64,
+             "mcl_spatial_workspace_bytes": C.c_int64, "mcl_spatial_columns": c_i}
 
 
 def _signature(name: str):
