@@ -1302,6 +1302,62 @@ int mcl_spatial_perm_summary(int32_t S, int32_t G, int32_t n_perms, const double
                              int32_t two_tailed, int32_t* count, double* pval_sim, double* pval_z_sim, double* mean_sim,
                              double* var_sim, void* stream);
 
+/* ---------------------------------------------------------------- Gaussian mixtures (csrc/mixture.hip)
+ * EM as sklearn's GaussianMixture states it, for S slides x R models per call.  Slide s owns rows offsets[s] ..
+ * offsets[s + 1] (device int64, S + 1 entries) of z (rows, D) fp64, row stride ld, and has k[s] components (device int32),
+ * 1 <= k[s] <= min(k_max, n_s), 1 <= n_s <= 50000; D <= 64 and k_max <= 64, MCL_EUNSUPPORTED beyond.  covariance_type:
+ * 0 full, 1 tied, 2 diag, 3 spherical; covariances and precisions_cholesky hold, per model, (k_max, D, D), (D, D),
+ * (k_max, D) or (k_max) doubles (full / tied: the upper-triangular factor P with P^T P = the precision).  fp64, no
+ * floating-point atomics, every sum in one fixed order that depends on the slide's own shape alone: a slide inside a batch
+ * is bit-identical to the same slide alone.  One workgroup runs one whole (model, slide) problem; none waits for another.
+ *
+ * mcl_gmm_workspace_bytes: the workspace of mcl_gmm_fit / mcl_gmm_select (R models) and of mcl_gmm_mstep (R = 1).
+ * mcl_gmm_fit: init_labels (R, rows) int32 are one-hot responsibilities (sklearn's _initialize), then E / M steps until
+ *   |change of lower_bound| < tol or max_iter, then one more E-step: labels_all (R, rows), the parameters (S, R, ...),
+ *   lower_bound_all / score_all (S, R): the mean log-likelihood of the last iteration's E-step / under the final parameters.
+ *   status_all (S, R): 0 ok; 1 a covariance was not positive definite (sklearn raises "ill-defined empirical covariance":
+ *   lower bound NaN, labels -1, the problem ends there); 2 the slide's shape or k breaks the statements above.
+ * mcl_gmm_select: per slide the model of highest lower bound (ties: lowest r; NaN never wins): its labels (rows), resp
+ *   (rows, k_max) = exp(log_resp), parameters (S, ...), n_iter, converged, status, restart, and bic / aic with sklearn's
+ *   parameter counts.
+ * mcl_gmm_predict: the E-step of the fit under given parameters (S, ...): log_prob_norm (rows) = score_samples, log_resp and
+ *   resp (rows, k_max), labels (argmax, ties to the lowest k), score (S) = the mean of log_prob_norm.
+ * mcl_gmm_mstep: the M-step of the fit from given log_resp (rows, k_max): weights = n_k / sum n_k, means, covariances
+ *   (+ reg_covar on the diagonal), precisions_cholesky; status (S) as above.
+ * mcl_cluster_validity: z as above with D <= 64, labels (rows) int32 in [0, 1024) or -1 = the row is dropped, 2 <= n_s <=
+ *   50000.  silhouette (rows): sklearn's silhouette_samples (Euclidean; 0 for a row alone in its cluster, NaN for a dropped
+ *   row); scores (S, 3): the mean silhouette over the kept rows, the Calinski-Harabasz and the Davies-Bouldin score, NaN
+ *   all three when the slide has fewer than 2 or more than kept - 1 non-empty clusters (or a label out of range).  work:
+ *   mcl_cluster_validity_workspace_bytes.  Every (row, cluster) distance sum runs over the cluster's rows ascending.
+ * The stream is typed void* (a hipStream_t) for the reason given at mcl_leiden_init.                                     */
+int64_t mcl_gmm_workspace_bytes(int64_t rows, int32_t S, int32_t R, int32_t D, int32_t k_max);
+int mcl_gmm_fit(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
+                const int32_t* k, int32_t k_max, int32_t R, int32_t covariance_type, const int32_t* init_labels,
+                double tol, int32_t max_iter, double reg_covar, void* work, int64_t work_bytes, int32_t* labels_all,
+                double* weights_all, double* means_all, double* covariances_all, double* precisions_cholesky_all,
+                double* lower_bound_all, double* score_all, int32_t* n_iter_all, int32_t* converged_all,
+                int32_t* status_all, void* stream);
+int mcl_gmm_select(const int64_t* offsets, int32_t S, int64_t rows, int32_t D, const int32_t* k, int32_t k_max, int32_t R,
+                   int32_t covariance_type, const void* work, int64_t work_bytes, const int32_t* labels_all,
+                   const double* weights_all, const double* means_all, const double* covariances_all,
+                   const double* precisions_cholesky_all, const double* lower_bound_all, const double* score_all,
+                   const int32_t* n_iter_all, const int32_t* converged_all, const int32_t* status_all, int32_t* labels,
+                   double* resp, double* weights, double* means, double* covariances, double* precisions_cholesky,
+                   double* lower_bound, int32_t* n_iter, int32_t* converged, int32_t* status, double* bic, double* aic,
+                   int32_t* restart, void* stream);
+int mcl_gmm_predict(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
+                    const int32_t* k, int32_t k_max, int32_t covariance_type, const double* weights, const double* means,
+                    const double* precisions_cholesky, double* log_prob_norm, double* log_resp, double* resp,
+                    int32_t* labels, double* score, void* stream);
+int mcl_gmm_mstep(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D, const int32_t* k,
+                  int32_t k_max, int32_t covariance_type, const double* log_resp, double reg_covar, void* work,
+                  int64_t work_bytes, double* weights, double* means, double* covariances, double* precisions_cholesky,
+                  int32_t* status, void* stream);
+int64_t mcl_cluster_validity_workspace_bytes(int64_t rows, int32_t S, int32_t D);
+int mcl_cluster_validity(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
+                         const int32_t* labels, void* work, int64_t work_bytes, double* silhouette, double* scores,
+                         void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

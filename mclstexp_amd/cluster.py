@@ -16,7 +16,7 @@ kernel's own k-means++ (counter-based generator) is used, best of ``n_init`` res
 the HIP library these functions raise ``RuntimeError``.
 
     python -m mclstexp_amd.cluster --pred P1.npy ... --labels L1.npy ... [--n_init N] [--json OUT] [--tsne OUT.npz]
-                                  [--pca_solver {host,device}]
+                                  [--pca_solver {host,device}] [--method {kmeans,gmm}]
 """
 from __future__ import annotations
 
@@ -37,6 +37,7 @@ MAX_ROWS = 50000     # per segment: the pair counts of the ARI stay inside int64
 MAX_LABEL = 1024     # label values in [0, 1024)
 MAX_TABLE = 12288    # distinct(a) * distinct(b) per segment
 SOLVERS = ("host", "device")   # of the PCA's symmetric eigenproblem: numpy.linalg.eigh / mclstexp_amd.eig
+METHODS = ("kmeans", "gmm")    # of the clustering of the scores: Lloyd / mclstexp_amd.mixture (full covariance)
 
 
 def validate_offsets(offsets: Optional[Sequence[int]], rows: int, min_rows: int = 1) -> np.ndarray:
@@ -281,16 +282,21 @@ def _take_rows(x: ArrayLike, idx: np.ndarray, dev: torch.device) -> ArrayLike:
 def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undetermined="undetermined",
                    n_comps: int = N_COMPS, seed_rows=None, n_init: int = 1, seed: int = 0, tol: float = 1e-4,
                    max_iter: int = 300, segment_base: int = 0, tsne: Union[bool, dict] = False,
-                   solver: str = "host") -> Dict[str, object]:
+                   solver: str = "host", method: str = "kmeans") -> Dict[str, object]:
     """cluster() for every slide of an evaluation in ONE gram / ONE project / ONE kmeans / ONE scores call.
     ``preds[i]``: (spots_i, genes) predicted expression, ``labels[i]``: (spots_i,) annotations.  Returns ``slides``: per
     slide ``p`` (cluster index per kept spot, int32), ``ari``, ``nmi`` (rounded to 3 decimals as the reference does),
     ``ari_raw``, ``nmi_raw``, ``k``, ``inertia``, ``n_iter``, ``restart``; and ``ari``, ``nmi``: the means over slides of
     the rounded values.  ``tsne`` (True, or a dict of ``mclstexp_amd.tsne.tsne`` arguments): every slide also gets ``tsne``,
     the (kept spots, 2) exact t-SNE embedding of its PCA scores (the reference's ``sc.tl.tsne``), as a numpy array;
-    everything else is what ``tsne=False`` gives.  ``solver``: the PCA's eigensolver (see ``pca_device``)."""
+    everything else is what ``tsne=False`` gives.  ``solver``: the PCA's eigensolver (see ``pca_device``).  ``method``:
+    ``"gmm"`` hands the labels of every k-means restart to ``mclstexp_amd.mixture.gmm`` (full covariance, its default
+    ``tol`` / ``max_iter``) as starts and scores the mixture's labels: ``restart`` is then the start of highest lower
+    bound, ``n_iter`` EM's, ``inertia`` NaN, and every slide also gets ``lower_bound`` and ``bic``."""
     if solver not in SOLVERS:
         raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
+    if method not in METHODS:
+        raise ValueError(f"method must be one of {METHODS}, got {method!r}")
     if len(preds) != len(labels) or not len(preds):
         raise ValueError(f"need one label vector per prediction and >= 1 slide; got {len(preds)} and {len(labels)}")
     enc = []
@@ -307,6 +313,11 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
     z = pca_scores(x, off, n_comps, solver)
     km = kmeans(z, ks, off, seed_rows=seed_rows, n_init=n_init, seed=seed, tol=tol, max_iter=max_iter,
                 segment_base=segment_base)
+    if method == "gmm":
+        from . import mixture                         # mixture imports this module
+        gm = mixture.gmm(z, ks, off, init_labels=km["labels_all"])
+        km = {"labels": gm["labels"], "inertia": torch.full_like(gm["lower_bound"], float("nan")), "n_iter": gm["n_iter"],
+              "restart": gm["restart"]}
     truth = upload(np.concatenate([e[1] for e in enc]), dev)
     ari, nmi = cluster_scores(truth, km["labels"], off)
     p_all = km["labels"].cpu().numpy()
@@ -314,6 +325,10 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
     slides = [{"p": p_all[off[i]:off[i + 1]].copy(), "ari": round(float(ari[i]), 3), "nmi": round(float(nmi[i]), 3),
                "ari_raw": float(ari[i]), "nmi_raw": float(nmi[i]), "k": int(ks[i]), "inertia": float(inertia[i]),
                "n_iter": int(n_iter[i]), "restart": int(restart[i])} for i in range(len(preds))]
+    if method == "gmm":
+        lower_bound, bic = gm["lower_bound"].cpu().numpy(), gm["bic"].cpu().numpy()
+        for i, s in enumerate(slides):
+            s["lower_bound"], s["bic"] = float(lower_bound[i]), float(bic[i])
     if tsne is not False and tsne is not None:
         from . import tsne as tsne_module             # tsne imports this module
         emb = tsne_module.tsne(z, off, **(tsne if isinstance(tsne, dict) else {}))["embedding"].cpu().numpy()
@@ -324,14 +339,16 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
 
 
 def cluster(pred: ArrayLike, label: Sequence, undetermined="undetermined", n_comps: int = N_COMPS, seed_rows=None,
-            n_init: int = 1, seed: int = 0, tsne: Union[bool, dict] = False, solver: str = "host") -> tuple:
+            n_init: int = 1, seed: int = 0, tsne: Union[bool, dict] = False, solver: str = "host",
+            method: str = "kmeans") -> tuple:
     """The reference's ``cluster(adata, label)`` -> ``(p, ari, nmi)``: ``p`` the cluster index of every kept spot,
     ``ari`` / ``nmi`` rounded to 3 decimals.  ``seed_rows`` (n_restarts, k) or (k,): initial centres as rows of the kept
-    spots.  ``tsne`` (see ``cluster_slides``): ``(p, ari, nmi, embedding)``.  ``solver``: see ``pca_device``."""
+    spots.  ``tsne`` (see ``cluster_slides``): ``(p, ari, nmi, embedding)``.  ``solver``: see ``pca_device``; ``method``: see
+    ``cluster_slides``."""
     if seed_rows is not None:
         seed_rows = [np.asarray(seed_rows)]
     s = cluster_slides([pred], [label], undetermined, n_comps, seed_rows, n_init, seed, tsne=tsne,
-                       solver=solver)["slides"][0]
+                       solver=solver, method=method)["slides"][0]
     if "tsne" in s:
         return s["p"], s["ari"], s["nmi"], s["tsne"]
     return s["p"], s["ari"], s["nmi"]
@@ -353,6 +370,8 @@ def parse_args(argv: Optional[Sequence[str]] = None) -> argparse.Namespace:
                    help="also embed every slide's PCA scores by exact t-SNE and write slide_<i> arrays (kept spots, 2)")
     p.add_argument("--pca_solver", choices=SOLVERS, default="host",
                    help="eigensolver of the PCA: numpy.linalg.eigh on the host (default) or mclstexp_amd.eig on the GPU")
+    p.add_argument("--method", choices=METHODS, default="kmeans",
+                   help="cluster the PCA scores by k-means (default) or by a Gaussian mixture started from it")
     a = p.parse_args(argv)
     if len(a.pred) != len(a.labels):
         p.error(f"{len(a.pred)} --pred files but {len(a.labels)} --labels files")
@@ -371,7 +390,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     preds = [np.load(f) for f in a.pred]
     labels = [np.load(f, allow_pickle=False) for f in a.labels]
     res = cluster_slides(preds, labels, a.undetermined, a.n_comps, None, a.n_init, a.seed, tsne=a.tsne is not None,
-                         solver=a.pca_solver)
+                         solver=a.pca_solver, method=a.method)
     print(format_report(res))
     if a.tsne:
         np.savez(a.tsne, **{f"slide_{i}": s.pop("tsne") for i, s in enumerate(res["slides"])})
