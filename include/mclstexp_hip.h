@@ -1358,6 +1358,48 @@ int mcl_cluster_validity(const double* z, int64_t ld, const int64_t* offsets, in
                          const int32_t* labels, void* work, int64_t work_bytes, double* silhouette, double* scores,
                          void* stream);
 
+/* ---------------------------------------------------------------- Potts-HMRF mixtures (csrc/hmrf.hip)
+ * The mixture above with a Potts prior on the labels over a fixed-width neighbour list: nbr (rows, kw) int32, indices local
+ * to the slide, w (rows, kw) fp64 with 0 marking a pruned slot (what mcl_spatial_lattice writes), kw <= 64, and one coupling
+ * beta[s] >= 0 per slide (device fp64).  Mean-field EM in synchronous sweeps: the field of iteration t,
+ * f_ik = sum over the kept slots c ascending of w_ic q[nbr_ic][k], reads the responsibilities q of iteration t - 1; the
+ * E-step normalises the mixture's weighted log prob + (beta f).  Shapes and limits as the mixture's, with n_s <= 16384.  A
+ * kept slot whose index lies outside 0 .. n_s - 1 counts as pruned and sets bit 4 (value 4) of the status.
+ *
+ * mcl_hmrf_workspace_bytes: the workspace of mcl_hmrf_fit.  It begins with the one mcl_gmm_workspace_bytes describes, so
+ *   mcl_gmm_select reads it as it is; the field (R, rows, k_max) of every start's final E-step follows at byte
+ *   mcl_gmm_workspace_bytes(rows, S, R, D, k_max).
+ * mcl_hmrf_fit: mcl_gmm_fit with the graph and beta.  lower_bound_all / score_all (S, R): the mean over the rows of
+ *   lse_i - za_i (the mean-field pseudo-log-likelihood; za the log-sum-exp of log w_k + (beta f_ik)) of the last iteration /
+ *   under the final parameters; the bic / aic mcl_gmm_select derives from score_all are pseudo-likelihood criteria.
+ *   status_all: 0, 1, 2 as mcl_gmm_fit (2 also for a beta that is negative or not finite), bit 4 as above.
+ * mcl_hmrf_estep: one E-step under given parameters (S, ...) and previous responsibilities resp_prev (rows, k_max): field,
+ *   log_resp, resp (rows, k_max), labels (argmax, ties to the lowest k), log_prob_norm = lse and log_prior_norm = za (rows),
+ *   score (S) = the mean of lse - za, status (S).
+ * mcl_label_refine: one synchronous round of majority relabelling.  For a spot with label l >= 0: over its kept slots
+ *   whose neighbour's label is >= 0 (m of them) and the spot itself, own = the count of l, top = the label of largest
+ *   count (ties: the smallest label); the spot takes top iff 2 own < m and 2 count(top) > m.  -1 stays -1.  Every decision
+ *   reads labels; labels_out (rows) must not alias it; changed (S): the spots whose label changed.
+ * mcl_edge_agreement: sums (S, 2): sum_i sum_c w_ic [l_i = l_nbr] and sum_i sum_c w_ic, both over the kept slots whose two
+ *   labels are >= 0; slots ascending within a row, rows summed per thread t, t + 256, ... and then in a binary tree.
+ * The stream is typed void* (a hipStream_t) for the reason given at mcl_leiden_init.                                     */
+int64_t mcl_hmrf_workspace_bytes(int64_t rows, int32_t S, int32_t R, int32_t D, int32_t k_max);
+int mcl_hmrf_fit(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
+                 const int32_t* k, int32_t k_max, int32_t R, int32_t covariance_type, const int32_t* init_labels,
+                 const int32_t* nbr, const double* w, int32_t kw, const double* beta, double tol, int32_t max_iter,
+                 double reg_covar, void* work, int64_t work_bytes, int32_t* labels_all, double* weights_all,
+                 double* means_all, double* covariances_all, double* precisions_cholesky_all, double* lower_bound_all,
+                 double* score_all, int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all, void* stream);
+int mcl_hmrf_estep(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
+                   const int32_t* k, int32_t k_max, int32_t covariance_type, const double* weights, const double* means,
+                   const double* precisions_cholesky, const double* resp_prev, const int32_t* nbr, const double* w,
+                   int32_t kw, const double* beta, double* field, double* log_resp, double* resp, int32_t* labels,
+                   double* log_prob_norm, double* log_prior_norm, double* score, int32_t* status, void* stream);
+int mcl_label_refine(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
+                     const double* w, int32_t kw, int32_t* labels_out, int32_t* changed, void* stream);
+int mcl_edge_agreement(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
+                       const double* w, int32_t kw, double* sums, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

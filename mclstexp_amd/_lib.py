@@ -289,6 +289,14 @@ PROTOTYPES = {
     "mcl_gmm_mstep": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_d, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_cluster_validity_workspace_bytes": [c_l, c_i, c_i],
     "mcl_cluster_validity": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_p, c_l, c_p, c_p, c_p],
+    # csrc/hmrf.hip: the stream is a plain trailing c_p as for leiden; hmrf.py passes current_stream()
+    "mcl_hmrf_workspace_bytes": [c_l, c_i, c_i, c_i, c_i],
+    "mcl_hmrf_fit": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_d, c_i, c_d, c_p, c_l,
+                     c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_hmrf_estep": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
+                       c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_label_refine": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_p],
+    "mcl_edge_agreement": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -306,7 +314,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_umap_workspace_bytes": C.c_int64, "mcl_leiden_workspace_bytes": C.c_int64,
              "mcl_sym_eig_workspace_bytes": C.c_int64, "mcl_marker_workspace_bytes": C.c_int64,
              "mcl_spatial_workspace_bytes": C.c_int64, "mcl_spatial_columns": c_i,
-             "mcl_gmm_workspace_bytes": C.c_int64, "mcl_cluster_validity_workspace_bytes": C.c_int64}
+             "mcl_gmm_workspace_bytes": C.c_int64, "mcl_cluster_validity_workspace_bytes": C.c_int64,
+             "mcl_hmrf_workspace_bytes": C.c_int64}
 
 
 def _signature(name: str):
