@@ -1400,6 +1400,57 @@ int mcl_label_refine(const int64_t* offsets, int32_t S, int64_t rows, const int3
 int mcl_edge_agreement(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
                        const double* w, int32_t kw, double* sums, void* stream);
 
+/* ---------------------------------------------------------------- ligand-receptor permutation test (csrc/ligrec.hip)
+ * squidpy.gr.ligrec / CellPhoneDB: group means of the ligand and receptor genes under permutations of the group labels.
+ * Slide s owns rows offsets[s] .. offsets[s + 1] (device int64, S + 1 entries) of x (rows, G; dtype 0 fp32, 1 fp64; row
+ * stride ld) and labels (rows,) int32 in -1 .. k[s] - 1 (-1: the spot is dropped; k device int32 per slide, <= kmax).
+ * 2 <= n_s <= max_n <= 16384 (the limit of mcl_spatial_permutations, whose tables it reads), kmax <= 255, G <= 16384,
+ * n_perms <= 65535, S <= 32767, I <= 65535, I kmax^2 <= 2^24 and S I kmax^2 < 2^31: MCL_EUNSUPPORTED beyond, MCL_EINVAL for a
+ * malformed call.  The KEPT spots n of a slide (label >= 0) may number 0 or 1: mcl_spatial_permutations then skips the slide
+ * (it gets no table), and a slide of one kept spot takes the identity as its only permutation, a slide of none has NaN
+ * means and no defined entry.  fp64, every group sum in one fixed order
+ * that depends on the group's size alone, no floating-point atomics; a slide inside a batch is bit-identical to the same slide
+ * alone.  status (S, 4): offsets or k broken, labels outside -1 .. k - 1 (dropped), non-finite x, negative x (the last two
+ * counted over the kept spots of the used columns).  The stream is typed void* (a hipStream_t) as at mcl_leiden_init.
+ *
+ * mcl_ligrec_columns: the used gene columns (1, 2, 4 or 8) a workgroup of mcl_ligrec_group_means takes for n kept spots.
+ * mcl_ligrec_chunk: the permutations per chunk: as many as keep perm_means within 256 MiB, at most n_perms.
+ * mcl_ligrec_workspace_bytes: the bytes of perm_means, (S, chunk, U, kmax) fp64.
+ * mcl_ligrec_prepare: order (rows,): the kept spots of slide s (segment-local) in the stable order by (label, spot) at
+ *   offsets[s] .. + n, -1 behind them; start (S, kmax + 1): group c owns positions start[c] .. start[c + 1] of that order
+ *   (start[c] = n for c >= k[s]); kept_offsets (S + 1,): the running sum of n: the offsets to hand to
+ *   mcl_spatial_permutations, whose table then holds (n_perms, n) uint16 per slide at element n_perms * kept_offsets[s].
+ * mcl_ligrec_group_means: used (U,) int32: the ascending distinct gene columns of the interactions.  column_mask: bit c set
+ *   = launch the c-column kernel (the bits mcl_ligrec_columns gives for the slides' n).  table = NULL: the identity, once:
+ *   writes sum, nnz (count of values > 0), mean = sum / size and frac = nnz / size, all (S, kmax, U) (an empty group: NaN
+ *   mean and frac).  Otherwise permutations p0 .. p0 + pc - 1 (pc <= chunk) of the table: group c receives the spots
+ *   order[table[p][j]], start[c] <= j < start[c + 1]; perm_means[s][p - p0][u][c] is its mean.
+ * mcl_ligrec_observed: side t of interaction i lists the used-column indices members[member_offsets[2 i + t] ..
+ *   member_offsets[2 i + t + 1]) ascending; of a complex the member of lowest mean over the kept spots is taken (sum over
+ *   the groups ascending / n; ties: the first).  pairs (S, I, 2): the choice.  means, defined, count (S, I, kmax, kmax):
+ *   (m1 + m2) / 2 where both group means are > 0, else 0 (NaN with an empty or absent group); defined = both > 0 and both
+ *   nnz >= threshold * size; count = 0.
+ * mcl_ligrec_count: count[s][i][c1][c2] += the permutations p < pc of perm_means with
+ *   (m1' + m2') / 2 >= (m1 + m2) / 2; one thread owns an element.                                                          */
+int32_t mcl_ligrec_columns(int32_t n);
+int32_t mcl_ligrec_chunk(int32_t S, int32_t kmax, int32_t U, int32_t n_perms);
+int64_t mcl_ligrec_workspace_bytes(int32_t S, int32_t kmax, int32_t U, int32_t n_perms);
+int mcl_ligrec_prepare(const int64_t* offsets, const int32_t* labels, const int32_t* k, int32_t S, int64_t rows,
+                       int32_t max_n, int32_t kmax, int32_t* order, int32_t* start, int64_t* kept_offsets, int32_t* status,
+                       void* stream);
+int mcl_ligrec_group_means(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, const int64_t* kept_offsets,
+                           const int32_t* order, const int32_t* start, const int32_t* k, int32_t S, int64_t rows, int32_t G,
+                           int32_t max_n, int32_t kmax, const int32_t* used, int32_t U, int32_t column_mask,
+                           const void* table, int32_t n_perms, int32_t p0, int32_t pc, int32_t chunk, double* sum,
+                           int32_t* nnz, double* mean, double* frac, double* perm_means, int32_t* status, void* stream);
+int mcl_ligrec_observed(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const int32_t* start,
+                        const double* sum, const int32_t* nnz, const double* mean, const int32_t* member_offsets,
+                        const int32_t* members, double threshold, int32_t* pairs, double* means, int32_t* defined,
+                        int32_t* count, void* stream);
+int mcl_ligrec_count(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const double* mean,
+                     const int32_t* pairs, const double* perm_means, int32_t chunk, int32_t pc, int32_t* count,
+                     void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

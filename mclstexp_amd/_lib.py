@@ -297,6 +297,15 @@ PROTOTYPES = {
                        c_p, c_p, c_p, c_p, c_p, c_p],
     "mcl_label_refine": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_p],
     "mcl_edge_agreement": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p],
+    # csrc/ligrec.hip: the stream is a plain trailing c_p as for leiden; ligrec.py passes current_stream()
+    "mcl_ligrec_columns": [c_i],
+    "mcl_ligrec_chunk": [c_i, c_i, c_i, c_i],
+    "mcl_ligrec_workspace_bytes": [c_i, c_i, c_i, c_i],
+    "mcl_ligrec_prepare": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "mcl_ligrec_group_means": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i,
+                               c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "mcl_ligrec_observed": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_d, c_p, c_p, c_p, c_p, c_p],
+    "mcl_ligrec_count": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -315,7 +324,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_sym_eig_workspace_bytes": C.c_int64, "mcl_marker_workspace_bytes": C.c_int64,
              "mcl_spatial_workspace_bytes": C.c_int64, "mcl_spatial_columns": c_i,
              "mcl_gmm_workspace_bytes": C.c_int64, "mcl_cluster_validity_workspace_bytes": C.c_int64,
-             "mcl_hmrf_workspace_bytes": C.c_int64}
+             "mcl_hmrf_workspace_bytes": C.c_int64, "mcl_ligrec_columns": c_i, "mcl_ligrec_chunk": c_i,
+             "mcl_ligrec_workspace_bytes": C.c_int64}
 
 
 def _signature(name: str):
