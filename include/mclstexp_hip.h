@@ -1451,6 +1451,44 @@ int mcl_ligrec_count(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_
                      const int32_t* pairs, const double* perm_means, int32_t chunk, int32_t pc, int32_t* count,
                      void* stream);
 
+/* ---------------------------------------------------------------- arrangement of spot groups (ABI 13, entry points added;
+ * csrc/nhood.hip).  squidpy.gr.nhood_enrichment / interaction_matrix / co_occurrence: which groups sit next to
+ * which on the spot lattice under permutations of the group labels, and which lie within a radius of which.  offsets, labels,
+ * k, order, start and kept_offsets are those of mcl_ligrec_prepare, whose status (S, 4) these entry points extend: [2]
+ * counts the kept neighbour slots whose index lies outside the slide (they count as pruned), [3] the kept spots with a
+ * non-finite coordinate.  2 <= n_s <= max_n <= 16384, kmax <= 255, kw <= 64, n_perms <= 65535, T <= 64, S <= 32767, S kmax^2
+ * and S T kmax^2 < 2^31: MCL_EUNSUPPORTED beyond, MCL_EINVAL for a malformed call.  Everything is an integer count (and three
+ * fp64 divisions): bit-reproducible, a slide inside a batch is bit-identical to the same slide alone.  The stream is typed
+ * void* (a hipStream_t) as at mcl_leiden_init.
+ *
+ * mcl_nhood_tile_rows: the source groups a workgroup of mcl_nhood_counts takes for a slide of n rows and K groups:
+ *   (155648 - 2 ceil16(n)) / (32 K), at least 1, at most K.  mcl_nhood_staged: 1 when the slide's uint16 neighbour list
+ *   (2 n kw bytes) fits in LDS beside them, 0 when it is read through L2.
+ * mcl_nhood_workspace_bytes: the bytes of work: the uint16 neighbour list.
+ * mcl_nhood_counts: nbr (rows, kw) int32 slide-local, w (rows, kw) fp64, 0 = pruned.  count (S, kmax, kmax) int32:
+ *   count[c1][c2] = #(spot i, slot c) with w != 0, both ends kept, label(i) = c1, label(nbr) = c2.  table = NULL (n_perms 0):
+ *   that alone.  Otherwise the (n_perms, n) uint16 tables of mcl_spatial_permutations at element n_perms * kept_offsets[s]:
+ *   under permutation p the spot order[table[p][j]] belongs to the group that owns position j; stats (S, 4, kmax, kmax)
+ *   int64: sum of count_p, sum of count_p^2, #(count_p >= count), #(count_p <= count).
+ * mcl_cooccur_workspace_bytes: the bytes of work: the coordinates of the kept spots in sorted order.
+ * mcl_cooccur_counts: coords (rows, 2) fp64, radii_sq (S, T) fp64 ascending.  pairs (S, T, kmax, kmax) int32: the ordered
+ *   pairs i != j of kept spots with label(i) = c1, label(j) = c2 whose FIRST t with d2 <= radii_sq[t] is t; d2 = dx dx + dy dy,
+ *   every product and the sum rounded separately.
+ * mcl_cooccur_scores: pairs becomes its running sum over t in place; occ (S, T, kmax, kmax) fp64 = (pairs / row) / (col /
+ *   tot) with row, col, tot the sums of pairs[t] over c2, c1 and both; NaN where a denominator is 0 or a group is absent. */
+int32_t mcl_nhood_tile_rows(int32_t n, int32_t kmax);
+int32_t mcl_nhood_staged(int32_t n, int32_t kmax, int32_t kw);
+int64_t mcl_nhood_workspace_bytes(int64_t rows, int32_t kw);
+int mcl_nhood_counts(const int64_t* offsets, const int64_t* kept_offsets, const int32_t* order, const int32_t* start,
+                     const int32_t* k, int32_t S, int64_t rows, int32_t max_n, int32_t kmax, const int32_t* nbr,
+                     const double* w, int32_t kw, const void* table, int32_t n_perms, void* work, int32_t* count,
+                     int64_t* stats, int32_t* status, void* stream);
+int64_t mcl_cooccur_workspace_bytes(int64_t rows);
+int mcl_cooccur_counts(const double* coords, const int64_t* offsets, const int32_t* order, const int32_t* start,
+                       const int32_t* k, int32_t S, int64_t rows, int32_t max_n, int32_t kmax, const double* radii_sq,
+                       int32_t T, void* work, int32_t* pairs, int32_t* status, void* stream);
+int mcl_cooccur_scores(const int32_t* k, int32_t S, int32_t kmax, int32_t T, int32_t* pairs, double* occ, void* stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)
