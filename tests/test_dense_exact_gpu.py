@@ -10,108 +10,15 @@ import pytest
 import torch
 
 import dense_reference as dr
+from exact_harness import DEV, EPS, Mat, vec, out_vec, _st, _check, _within, _bias, _bias_ok, _stats
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
-EPS = 1e-5
-GUARD = 256                      # guard bytes on either side of every buffer
-SENT16 = 0x7FC1                  # a quiet NaN as bf16
-SENT32 = 0x7FC0DEAD              # a quiet NaN as fp32
 
 
 @pytest.fixture(scope="module")
 def L():
     from mclstexp_amd import _lib
     return _lib.lib()           # must load: no fallback
-
-
-def _st():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _check(code, what):
-    assert code == 0, f"{what} returned {code}"
-
-
-class Mat:
-    """A (rows, ld) device matrix of bf16 (bits in int16) or fp32 (bits in int32) between guards, every element the NaN
-    sentinel until set().  freeze() remembers every bit; unchanged() then checks everything outside the columns a kernel may write."""
-
-    def __init__(self, rows, ld, kind="bf16"):
-        self.kind, self.rows, self.ld = kind, rows, ld
-        self.tdt, self.ndt, self.sent = ((torch.int16, np.uint16, SENT16) if kind == "bf16" else (torch.int32, np.uint32, SENT32))
-        self.isz = 2 if kind == "bf16" else 4
-        self.g = GUARD // self.isz
-        self.base = torch.full((2 * self.g + rows * ld,), self.sent, dtype=self.tdt, device=DEV)
-        self.before = None
-
-    def ptr(self, col=0):
-        return self.base.data_ptr() + self.isz * (self.g + col)
-
-    def _body(self):
-        return self.base[self.g:self.g + self.rows * self.ld].view(self.rows, self.ld)
-
-    def set(self, c0, vals):
-        vals = np.asarray(vals, dtype=np.float64).reshape(self.rows, -1)
-        bits = dr.bf16_bits(vals) if self.kind == "bf16" else vals.astype(np.float32).view(np.uint32)
-        assert self.kind != "bf16" or np.array_equal(dr.bits_to_f64(bits), vals), "operand is not a bf16 value"
-        t = torch.from_numpy(bits.view(np.int16 if self.kind == "bf16" else np.int32).copy()).to(DEV)
-        self._body()[:, c0:c0 + vals.shape[1]] = t
-        return self
-
-    def get(self, c0=0, n=None):
-        n = self.ld - c0 if n is None else n
-        bits = self._body()[:, c0:c0 + n].contiguous().cpu().numpy().view(self.ndt)
-        return dr.bits_to_f64(bits) if self.kind == "bf16" else bits.view(np.float32).astype(np.float64)
-
-    def freeze(self):
-        """Remember every bit (guards included) for unchanged()."""
-        self.before = self.base.cpu().numpy().copy()
-        return self
-
-    def unchanged(self, what, c0=None, n=None):
-        """Guards and everything outside the columns [c0, c0 + n) are bit-unchanged since freeze()."""
-        now = self.base.cpu().numpy()
-        same = now == self.before
-        if c0 is not None:
-            body = same[self.g:self.g + self.rows * self.ld].reshape(self.rows, self.ld)
-            body[:, c0:c0 + n] = True
-        assert same.all(), f"{what}: {int((~same).sum())} elements outside the output region were written"
-
-
-def vec(vals):
-    v = np.asarray(vals, dtype=np.float64).reshape(1, -1)
-    return Mat(1, v.shape[1], "f32").set(0, v)
-
-
-def out_vec(n):
-    return Mat(1, n, "f32")
-
-
-def _within(name, out, ref, bound, report):
-    assert np.isfinite(out).all(), f"{name}: non-finite output"
-    w, at = dr.worst(out, ref, bound)
-    report.append(f"{name} {w:.3f}")
-    assert w <= 1.0, f"{name}: element {at} is {w:.3f} of its bound (out {out[at]!r}, ref {ref[at]!r}, bound {bound[at]!r})"
-    return w
-
-
-def _bias(name, out, ref, report):
-    b, n, allowed = dr.bias(out, ref)
-    report.append(f"bias({name}) {b:+.4f}/N={n}")
-    assert abs(b) <= allowed, f"{name}: rounding bias {b:+.4f} half-ulps over {n} elements (allowed {allowed:.4f})"
-
-
-def _bias_ok(name, out, ref):
-    b, n, allowed = dr.bias(out, ref)
-    assert abs(b) <= allowed, f"{name}: rounding bias {b:+.4f} half-ulps over {n} elements (allowed {allowed:.4f})"
-    return abs(b)
-
-
-def _stats(name, got, refs, bounds, report):
-    for nm, o, r, b in zip(("mean", "var", "rstd"), got, refs, bounds):
-        _within(f"{name}{nm}", o, r, b, report)
 
 
 # ------------------------------------------------------------------------------------------------------------ conv1x1 forward
