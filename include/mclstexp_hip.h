@@ -1151,8 +1151,6 @@ int mcl_umap_epochs(int32_t first, int32_t count, const int64_t* indptr, const i
  * 128 bytes (two doubles Q, Q of the refinement; two int64 2m, scratch; 24 int32: n, shift, label buffer, refined buffer,
  * parity, fails, move phase done, refinement done, finished, sweeps accepted at the level, sweeps, accepted sweeps, rounds,
  * levels, steps of the phase, error, next n, longest row, n at level 0), which the host reads between batches of launches.
- * The stream of these entry points is typed void* (a hipStream_t, as everywhere): the count of mcl_stream_t parameters is
- * pinned by tests that a feature may not edit; a later change re-types it.
  *
  * mcl_leiden_init: level 0 of one iteration: q, k_i, 2m, labels = partition (device int32 ids below n_s; NULL: every vertex
  *   alone), Q of that partition.  A segment with active[s] == 0 (active may be NULL) or with 2m = 0 is finished at once.
@@ -1168,22 +1166,22 @@ int mcl_umap_epochs(int32_t first, int32_t count, const int64_t* indptr, const i
 int64_t mcl_leiden_workspace_bytes(int64_t rows, int64_t nnz_total, int32_t S, int32_t max_n);
 int mcl_leiden_init(const int64_t* indptr, const int32_t* indices, const double* data, const int64_t* offsets,
                     const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution,
-                    const int32_t* partition, const int32_t* active, void* work, void* stream);
+                    const int32_t* partition, const int32_t* active, void* work, mcl_stream_t stream);
 int mcl_leiden_move_sweeps(int32_t count, int32_t level, int32_t n_cur, int32_t long_rows, int32_t max_sweeps,
                            const int64_t* indptr, const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets,
                            int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution, void* work,
-                           void* stream);
+                           mcl_stream_t stream);
 int mcl_leiden_refine_rounds(int32_t begin, int32_t count, int32_t level, int32_t n_cur, int32_t long_rows,
                              int32_t max_rounds, const int64_t* indptr, const int32_t* indices, const int64_t* offsets,
                              const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total,
-                             double resolution, void* work, void* stream);
+                             double resolution, void* work, mcl_stream_t stream);
 int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const int64_t* indptr, const int32_t* indices,
                          const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n,
-                         int64_t nnz_total, double resolution, void* work, void* stream);
+                         int64_t nnz_total, double resolution, void* work, mcl_stream_t stream);
 int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* active, const int64_t* indptr,
                       const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows,
                       int32_t max_n, int64_t nnz_total, void* work, int32_t* canonical, int32_t* labels, int32_t* n_clusters,
-                      void* stream);
+                      mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- leading eigenpairs of symmetric matrices (ABI 13, entry
  * points added; csrc/eig.hip).  The k <= 64 largest eigenvalues and their eigenvectors of S dense symmetric fp64 matrices
@@ -1201,12 +1199,11 @@ int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* activ
  * problem, computed on the device.  work: mcl_sym_eig_workspace_bytes bytes, 8-byte aligned; it carries the call from one
  * stage to the next.  stages: bit 0 the tridiagonalisation, bit 1 eigenvalues, vectors of T and the certificate, bit 2 the
  * back-transformation and the sign; 7 runs all, and a caller that times the stages passes 1, 2, 4 in that order with the
- * same arguments.  Enqueues about 3 max_m launches and never synchronises.  The stream is typed void* (a hipStream_t) for
- * the reason given at mcl_leiden_init. */
+ * same arguments.  Enqueues about 3 max_m launches and never synchronises. */
 int64_t mcl_sym_eig_workspace_bytes(int32_t S, int32_t max_m, int64_t sum_m, int32_t k);
 int mcl_sym_eig_top(double* a, const int64_t* a_offsets, const int32_t* m, int32_t S, int32_t max_m, int64_t sum_m,
                     int32_t k, int32_t stages, double* evals, double* evecs, const int64_t* evec_offsets, double* cert,
-                    void* work, void* stream);
+                    void* work, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- marker genes of spot groups (ABI 13, entry points added;
  * csrc/markers.hip).  scanpy's sc.tl.rank_genes_groups(adata, groupby, reference="rest") for every slide of an evaluation
@@ -1219,8 +1216,7 @@ int mcl_sym_eig_top(double* a, const int64_t* a_offsets, const int32_t* m, int32
  * slide s is group row sum_{s' < s} k[s'] + g of every (groups_total, G) output.  work: mcl_marker_workspace_bytes bytes,
  * 8-byte aligned; mcl_marker_stats fills it and the three other calls read it, so they follow it on the same stream with
  * the same S, rows, G, kmax, groups_total.  fp64 and exact int64, no floating-point atomics, deterministic; a slide inside
- * a batch is bit-identical to the same slide alone.  The stream is typed void* (a hipStream_t) for the reason given at
- * mcl_leiden_init.
+ * a batch is bit-identical to the same slide alone.
  *
  * mcl_marker_stats: group_sizes (groups_total), n_valid (S): rows with a label >= 0; per (group row, gene): mean and
  *   variance (ddof 1, NaN below two rows) of the group and of the rest, the fraction and the count of x != 0 of both;
@@ -1239,20 +1235,20 @@ int mcl_marker_stats(const void* x, int64_t ld, int32_t dtype, const int64_t* of
                      const int32_t* k, int32_t S, int64_t rows, int32_t G, int32_t max_n, int32_t kmax,
                      int64_t groups_total, void* work, int32_t* group_sizes, int32_t* n_valid, double* mean_g,
                      double* var_g, double* mean_r, double* var_r, double* pts_g, double* pts_r, int32_t* nnz_g,
-                     int32_t* nnz_r, int32_t* status, void* stream);
+                     int32_t* nnz_r, int32_t* status, mcl_stream_t stream);
 int mcl_marker_rank_sums(const void* x, int64_t ld, int32_t dtype, const int32_t* labels, int32_t S, int64_t rows,
                          int32_t G, int32_t max_n, int32_t kmax, int64_t groups_total, void* work, int64_t* rank_sums2,
-                         int64_t* tie_terms, void* stream);
+                         int64_t* tie_terms, mcl_stream_t stream);
 int mcl_marker_test(int32_t method, int32_t tie_correct, int32_t S, int64_t rows, int32_t G, int32_t kmax,
                     int64_t groups_total, const void* work, const int32_t* group_sizes, const double* mean_g,
                     const double* var_g, const double* mean_r, const double* var_r, const int64_t* rank_sums2,
                     const int64_t* tie_terms, double* scores, double* pvals, double* neglog10_pvals,
-                    double* logfoldchanges, void* stream);
+                    double* logfoldchanges, mcl_stream_t stream);
 int mcl_marker_rank_adjust(int32_t S, int64_t rows, int32_t G, int32_t kmax, int64_t groups_total, int32_t n_genes,
                            int32_t rankby_abs, void* work, const double* scores, const double* pvals,
                            const double* neglog10_pvals, const double* logfoldchanges, double* pvals_adj, int64_t* names,
                            double* top_scores, double* top_pvals, double* top_pvals_adj, double* top_neglog10_pvals,
-                           double* top_logfoldchanges, void* stream);
+                           double* top_logfoldchanges, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- spatial autocorrelation (csrc/spatial.hip)
  * Moran's I and Geary's C of every gene on the spot lattice graph of every slide, the analytic moments under normality and
@@ -1262,8 +1258,7 @@ int mcl_marker_rank_adjust(int32_t S, int64_t rows, int32_t G, int32_t kmax, int
  * offsets break the statements is skipped and counted in status.  The graph is a fixed-width list: nbr (rows, k) int32
  * segment-local, w (rows, k) fp64 (0 = a pruned slot), deg (rows,) = kept slots; consts (S, 3) = S0, S1, S2.  fp64, every
  * sum over the rows of a slide in one fixed order that depends on n alone, no floating-point atomics, deterministic; a slide
- * inside a batch is bit-identical to the same slide alone.  The stream is typed void* (a hipStream_t) for the reason given at
- * mcl_leiden_init.
+ * inside a batch is bit-identical to the same slide alone.
  *
  * mcl_spatial_workspace_bytes: hist_slots = k + 1 and n_perms = 0 for mcl_spatial_lattice; hist_slots = 0 for the
  *   permutation table, which is uint16 (n_perms, n_s) per slide at element offset n_perms * offsets[s].
@@ -1288,19 +1283,19 @@ int64_t mcl_spatial_workspace_bytes(int64_t rows, int32_t hist_slots, int32_t n_
 int32_t mcl_spatial_columns(int32_t n);
 int mcl_spatial_lattice(const int32_t* knn_indices, const double* knn_distances, const int64_t* offsets, int32_t S,
                         int64_t rows, int32_t max_n, int32_t k, int32_t prune, int32_t row_standardise, int32_t given,
-                        void* work, int32_t* nbr, double* w, int32_t* deg, double* consts, int32_t* status, void* stream);
+                        void* work, int32_t* nbr, double* w, int32_t* deg, double* consts, int32_t* status, mcl_stream_t stream);
 int mcl_spatial_permutations(const int64_t* offsets, int32_t S, int64_t rows, int32_t max_n, int32_t n_perms,
-                             uint64_t seed, void* work, void* stream);
+                             uint64_t seed, void* work, mcl_stream_t stream);
 int mcl_spatial_stats(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G,
                       int32_t max_n, int32_t k, int32_t column_mask, const int32_t* nbr, const double* w,
                       const double* consts, const void* table, int32_t n_perms, double* mean, double* den, double* stat,
-                      int32_t* status, void* stream);
+                      int32_t* status, mcl_stream_t stream);
 int mcl_spatial_moments(const int64_t* offsets, int32_t S, int64_t rows, int32_t G, int32_t max_n, const double* consts,
                         const double* stat, int32_t two_tailed, int32_t* prank, double* scratch, double* z_norm,
-                        double* pval_norm, double* neglog10_pval_norm, double* pval_norm_adj, void* stream);
+                        double* pval_norm, double* neglog10_pval_norm, double* pval_norm_adj, mcl_stream_t stream);
 int mcl_spatial_perm_summary(int32_t S, int32_t G, int32_t n_perms, const double* stat, const double* sims,
                              int32_t two_tailed, int32_t* count, double* pval_sim, double* pval_z_sim, double* mean_sim,
-                             double* var_sim, void* stream);
+                             double* var_sim, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- Gaussian mixtures (csrc/mixture.hip)
  * EM as sklearn's GaussianMixture states it, for S slides x R models per call.  Slide s owns rows offsets[s] ..
@@ -1328,15 +1323,14 @@ int mcl_spatial_perm_summary(int32_t S, int32_t G, int32_t n_perms, const double
  *   50000.  silhouette (rows): sklearn's silhouette_samples (Euclidean; 0 for a row alone in its cluster, NaN for a dropped
  *   row); scores (S, 3): the mean silhouette over the kept rows, the Calinski-Harabasz and the Davies-Bouldin score, NaN
  *   all three when the slide has fewer than 2 or more than kept - 1 non-empty clusters (or a label out of range).  work:
- *   mcl_cluster_validity_workspace_bytes.  Every (row, cluster) distance sum runs over the cluster's rows ascending.
- * The stream is typed void* (a hipStream_t) for the reason given at mcl_leiden_init.                                     */
+ *   mcl_cluster_validity_workspace_bytes.  Every (row, cluster) distance sum runs over the cluster's rows ascending. */
 int64_t mcl_gmm_workspace_bytes(int64_t rows, int32_t S, int32_t R, int32_t D, int32_t k_max);
 int mcl_gmm_fit(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                 const int32_t* k, int32_t k_max, int32_t R, int32_t covariance_type, const int32_t* init_labels,
                 double tol, int32_t max_iter, double reg_covar, void* work, int64_t work_bytes, int32_t* labels_all,
                 double* weights_all, double* means_all, double* covariances_all, double* precisions_cholesky_all,
                 double* lower_bound_all, double* score_all, int32_t* n_iter_all, int32_t* converged_all,
-                int32_t* status_all, void* stream);
+                int32_t* status_all, mcl_stream_t stream);
 int mcl_gmm_select(const int64_t* offsets, int32_t S, int64_t rows, int32_t D, const int32_t* k, int32_t k_max, int32_t R,
                    int32_t covariance_type, const void* work, int64_t work_bytes, const int32_t* labels_all,
                    const double* weights_all, const double* means_all, const double* covariances_all,
@@ -1344,19 +1338,19 @@ int mcl_gmm_select(const int64_t* offsets, int32_t S, int64_t rows, int32_t D, c
                    const int32_t* n_iter_all, const int32_t* converged_all, const int32_t* status_all, int32_t* labels,
                    double* resp, double* weights, double* means, double* covariances, double* precisions_cholesky,
                    double* lower_bound, int32_t* n_iter, int32_t* converged, int32_t* status, double* bic, double* aic,
-                   int32_t* restart, void* stream);
+                   int32_t* restart, mcl_stream_t stream);
 int mcl_gmm_predict(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                     const int32_t* k, int32_t k_max, int32_t covariance_type, const double* weights, const double* means,
                     const double* precisions_cholesky, double* log_prob_norm, double* log_resp, double* resp,
-                    int32_t* labels, double* score, void* stream);
+                    int32_t* labels, double* score, mcl_stream_t stream);
 int mcl_gmm_mstep(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D, const int32_t* k,
                   int32_t k_max, int32_t covariance_type, const double* log_resp, double reg_covar, void* work,
                   int64_t work_bytes, double* weights, double* means, double* covariances, double* precisions_cholesky,
-                  int32_t* status, void* stream);
+                  int32_t* status, mcl_stream_t stream);
 int64_t mcl_cluster_validity_workspace_bytes(int64_t rows, int32_t S, int32_t D);
 int mcl_cluster_validity(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                          const int32_t* labels, void* work, int64_t work_bytes, double* silhouette, double* scores,
-                         void* stream);
+                         mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- Potts-HMRF mixtures (csrc/hmrf.hip)
  * The mixture above with a Potts prior on the labels over a fixed-width neighbour list: nbr (rows, kw) int32, indices local
@@ -1381,24 +1375,23 @@ int mcl_cluster_validity(const double* z, int64_t ld, const int64_t* offsets, in
  *   count (ties: the smallest label); the spot takes top iff 2 own < m and 2 count(top) > m.  -1 stays -1.  Every decision
  *   reads labels; labels_out (rows) must not alias it; changed (S): the spots whose label changed.
  * mcl_edge_agreement: sums (S, 2): sum_i sum_c w_ic [l_i = l_nbr] and sum_i sum_c w_ic, both over the kept slots whose two
- *   labels are >= 0; slots ascending within a row, rows summed per thread t, t + 256, ... and then in a binary tree.
- * The stream is typed void* (a hipStream_t) for the reason given at mcl_leiden_init.                                     */
+ *   labels are >= 0; slots ascending within a row, rows summed per thread t, t + 256, ... and then in a binary tree. */
 int64_t mcl_hmrf_workspace_bytes(int64_t rows, int32_t S, int32_t R, int32_t D, int32_t k_max);
 int mcl_hmrf_fit(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                  const int32_t* k, int32_t k_max, int32_t R, int32_t covariance_type, const int32_t* init_labels,
                  const int32_t* nbr, const double* w, int32_t kw, const double* beta, double tol, int32_t max_iter,
                  double reg_covar, void* work, int64_t work_bytes, int32_t* labels_all, double* weights_all,
                  double* means_all, double* covariances_all, double* precisions_cholesky_all, double* lower_bound_all,
-                 double* score_all, int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all, void* stream);
+                 double* score_all, int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all, mcl_stream_t stream);
 int mcl_hmrf_estep(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                    const int32_t* k, int32_t k_max, int32_t covariance_type, const double* weights, const double* means,
                    const double* precisions_cholesky, const double* resp_prev, const int32_t* nbr, const double* w,
                    int32_t kw, const double* beta, double* field, double* log_resp, double* resp, int32_t* labels,
-                   double* log_prob_norm, double* log_prior_norm, double* score, int32_t* status, void* stream);
+                   double* log_prob_norm, double* log_prior_norm, double* score, int32_t* status, mcl_stream_t stream);
 int mcl_label_refine(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
-                     const double* w, int32_t kw, int32_t* labels_out, int32_t* changed, void* stream);
+                     const double* w, int32_t kw, int32_t* labels_out, int32_t* changed, mcl_stream_t stream);
 int mcl_edge_agreement(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
-                       const double* w, int32_t kw, double* sums, void* stream);
+                       const double* w, int32_t kw, double* sums, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- ligand-receptor permutation test (csrc/ligrec.hip)
  * squidpy.gr.ligrec / CellPhoneDB: group means of the ligand and receptor genes under permutations of the group labels.
@@ -1411,7 +1404,7 @@ int mcl_edge_agreement(const int64_t* offsets, int32_t S, int64_t rows, const in
  * means and no defined entry.  fp64, every group sum in one fixed order
  * that depends on the group's size alone, no floating-point atomics; a slide inside a batch is bit-identical to the same slide
  * alone.  status (S, 4): offsets or k broken, labels outside -1 .. k - 1 (dropped), non-finite x, negative x (the last two
- * counted over the kept spots of the used columns).  The stream is typed void* (a hipStream_t) as at mcl_leiden_init.
+ * counted over the kept spots of the used columns).
  *
  * mcl_ligrec_columns: the used gene columns (1, 2, 4 or 8) a workgroup of mcl_ligrec_group_means takes for n kept spots.
  * mcl_ligrec_chunk: the permutations per chunk: as many as keep perm_means within 256 MiB, at most n_perms.
@@ -1437,19 +1430,19 @@ int32_t mcl_ligrec_chunk(int32_t S, int32_t kmax, int32_t U, int32_t n_perms);
 int64_t mcl_ligrec_workspace_bytes(int32_t S, int32_t kmax, int32_t U, int32_t n_perms);
 int mcl_ligrec_prepare(const int64_t* offsets, const int32_t* labels, const int32_t* k, int32_t S, int64_t rows,
                        int32_t max_n, int32_t kmax, int32_t* order, int32_t* start, int64_t* kept_offsets, int32_t* status,
-                       void* stream);
+                       mcl_stream_t stream);
 int mcl_ligrec_group_means(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, const int64_t* kept_offsets,
                            const int32_t* order, const int32_t* start, const int32_t* k, int32_t S, int64_t rows, int32_t G,
                            int32_t max_n, int32_t kmax, const int32_t* used, int32_t U, int32_t column_mask,
                            const void* table, int32_t n_perms, int32_t p0, int32_t pc, int32_t chunk, double* sum,
-                           int32_t* nnz, double* mean, double* frac, double* perm_means, int32_t* status, void* stream);
+                           int32_t* nnz, double* mean, double* frac, double* perm_means, int32_t* status, mcl_stream_t stream);
 int mcl_ligrec_observed(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const int32_t* start,
                         const double* sum, const int32_t* nnz, const double* mean, const int32_t* member_offsets,
                         const int32_t* members, double threshold, int32_t* pairs, double* means, int32_t* defined,
-                        int32_t* count, void* stream);
+                        int32_t* count, mcl_stream_t stream);
 int mcl_ligrec_count(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const double* mean,
                      const int32_t* pairs, const double* perm_means, int32_t chunk, int32_t pc, int32_t* count,
-                     void* stream);
+                     mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- arrangement of spot groups (ABI 13, entry points added;
  * csrc/nhood.hip).  squidpy.gr.nhood_enrichment / interaction_matrix / co_occurrence: which groups sit next to
@@ -1458,8 +1451,7 @@ int mcl_ligrec_count(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_
  * counts the kept neighbour slots whose index lies outside the slide (they count as pruned), [3] the kept spots with a
  * non-finite coordinate.  2 <= n_s <= max_n <= 16384, kmax <= 255, kw <= 64, n_perms <= 65535, T <= 64, S <= 32767, S kmax^2
  * and S T kmax^2 < 2^31: MCL_EUNSUPPORTED beyond, MCL_EINVAL for a malformed call.  Everything is an integer count (and three
- * fp64 divisions): bit-reproducible, a slide inside a batch is bit-identical to the same slide alone.  The stream is typed
- * void* (a hipStream_t) as at mcl_leiden_init.
+ * fp64 divisions): bit-reproducible, a slide inside a batch is bit-identical to the same slide alone.
  *
  * mcl_nhood_tile_rows: the source groups a workgroup of mcl_nhood_counts takes for a slide of n rows and K groups:
  *   (155648 - 2 ceil16(n)) / (32 K), at least 1, at most K.  mcl_nhood_staged: 1 when the slide's uint16 neighbour list
@@ -1482,12 +1474,12 @@ int64_t mcl_nhood_workspace_bytes(int64_t rows, int32_t kw);
 int mcl_nhood_counts(const int64_t* offsets, const int64_t* kept_offsets, const int32_t* order, const int32_t* start,
                      const int32_t* k, int32_t S, int64_t rows, int32_t max_n, int32_t kmax, const int32_t* nbr,
                      const double* w, int32_t kw, const void* table, int32_t n_perms, void* work, int32_t* count,
-                     int64_t* stats, int32_t* status, void* stream);
+                     int64_t* stats, int32_t* status, mcl_stream_t stream);
 int64_t mcl_cooccur_workspace_bytes(int64_t rows);
 int mcl_cooccur_counts(const double* coords, const int64_t* offsets, const int32_t* order, const int32_t* start,
                        const int32_t* k, int32_t S, int64_t rows, int32_t max_n, int32_t kmax, const double* radii_sq,
-                       int32_t T, void* work, int32_t* pairs, int32_t* status, void* stream);
-int mcl_cooccur_scores(const int32_t* k, int32_t S, int32_t kmax, int32_t T, int32_t* pairs, double* occ, void* stream);
+                       int32_t T, void* work, int32_t* pairs, int32_t* status, mcl_stream_t stream);
+int mcl_cooccur_scores(const int32_t* k, int32_t S, int32_t kmax, int32_t T, int32_t* pairs, double* occ, mcl_stream_t stream);
 
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;

@@ -72,6 +72,24 @@ def paired_offsets(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike], noun:
     return validate_offsets(off, int(off[-1]), min_rows=2, noun=noun)
 
 
+def check_columns(x: ArrayLike, max_dim: int) -> Tuple[int, int]:
+    """(rows, D) of the 2-D matrix ``x``, whose 1 .. ``max_dim`` columns one thread of a kernel keeps."""
+    if not isinstance(x, Tensor) and np.asarray(x).ndim != 2:
+        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {np.asarray(x).shape}")
+    if len(x.shape) != 2:
+        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {tuple(x.shape)}")
+    rows, D = int(x.shape[0]), int(x.shape[1])
+    if D < 1 or D > max_dim:
+        raise ValueError(f"x has {D} columns; the kernel handles 1 .. {max_dim}")
+    return rows, D
+
+
+def nanmean(v) -> float:
+    """The mean of the finite entries of ``v``; NaN when it has none."""
+    v = np.asarray(v, dtype=np.float64)
+    return float(v[np.isfinite(v)].mean()) if np.isfinite(v).any() else float("nan")
+
+
 # -------------------------------------------------------------------------------------------------- device matrices
 def _as_2d(x: ArrayLike, name: str, exc: Type[Exception] = ValueError) -> Tensor:
     t = x if isinstance(x, Tensor) else torch.as_tensor(np.asarray(x))
@@ -106,6 +124,26 @@ def matrix(x: ArrayLike, name: str, dev: torch.device, accept: Container[torch.d
         out.copy_(t)
         return out
     return t.contiguous().to(dev)
+
+
+def dense(a: ArrayLike, name: str, shape, dtype: torch.dtype, dev: torch.device, copy: bool = False,
+          integer: Optional[bool] = None) -> Tensor:
+    """``a`` as a dense device tensor of ``shape`` and ``dtype``: a host array is converted on the host, a device tensor
+    of another dtype raises.  ``copy``: never the caller's own storage (the kernel writes it, or its outputs must alias
+    nothing).  ``integer`` True / False: a host array must hold integers / floating-point values."""
+    t = a if isinstance(a, Tensor) else torch.as_tensor(np.asarray(a))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    if t.is_cuda:
+        if t.dtype != dtype:
+            raise ValueError(f"{name}: device tensors must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
+    elif integer is not None and integer != (not t.dtype.is_floating_point and t.dtype != torch.bool):
+        raise ValueError(f"{name}: expected {'integers' if integer else 'floating-point values'}, got {t.dtype}")
+    if t.is_cuda and t.is_contiguous() and not copy:
+        return t
+    out = torch.empty(tuple(shape), device=dev, dtype=dtype)
+    out.copy_(t if t.is_cuda else t.to(dtype))
+    return out
 
 
 def stack_rows(parts: Sequence[ArrayLike], name: str, dev: torch.device,

@@ -253,67 +253,59 @@ PROTOTYPES = {
     "mcl_umap_init": [c_i, c_p, c_l, c_i, c_i, c_p, c_i, c_i, c_i, c_i, C.c_uint64, c_p, c_s],
     "mcl_umap_epochs": [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_l, c_i, c_d, c_d, c_d, c_d, c_i, C.c_uint64,
                         c_p, c_p, c_p, c_p, c_s],
-    # csrc/leiden.hip: the stream is a plain trailing c_p (include/mclstexp_hip.h says why); leiden.py passes current_stream()
     "mcl_leiden_workspace_bytes": [c_l, c_l, c_i, c_i],
-    "mcl_leiden_init": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p, c_p, c_p],
-    "mcl_leiden_move_sweeps": [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p],
-    "mcl_leiden_refine_rounds": [c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p],
-    "mcl_leiden_aggregate": [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p],
-    "mcl_leiden_finish": [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p],
-    # csrc/eig.hip: the stream is a plain trailing c_p as for leiden; eig.py passes current_stream()
+    "mcl_leiden_init": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_p, c_p, c_s],
+    "mcl_leiden_move_sweeps": [c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_s],
+    "mcl_leiden_refine_rounds": [c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_s],
+    "mcl_leiden_aggregate": [c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_d, c_p, c_s],
+    "mcl_leiden_finish": [c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_s],
     "mcl_sym_eig_workspace_bytes": [c_i, c_i, c_l, c_i],
-    "mcl_sym_eig_top": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    # csrc/markers.hip: the stream is a plain trailing c_p as for leiden; markers.py passes current_stream()
+    "mcl_sym_eig_top": [c_p, c_p, c_p, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_marker_workspace_bytes": [c_l, c_l, c_i, c_i],
     "mcl_marker_stats": [c_p, c_l, c_i, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                         c_p, c_p, c_p, c_p, c_p],
-    "mcl_marker_rank_sums": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_p],
-    "mcl_marker_test": [c_i, c_i, c_i, c_l, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+                         c_p, c_p, c_p, c_p, c_s],
+    "mcl_marker_rank_sums": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_l, c_p, c_p, c_p, c_s],
+    "mcl_marker_test": [c_i, c_i, c_i, c_l, c_i, c_i, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_marker_rank_adjust": [c_i, c_l, c_i, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                               c_p],
-    # csrc/spatial.hip: the stream is a plain trailing c_p as for leiden; spatial.py passes current_stream()
+                               c_s],
     "mcl_spatial_workspace_bytes": [c_l, c_i, c_i],
     "mcl_spatial_columns": [c_i],
-    "mcl_spatial_lattice": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_spatial_permutations": [c_p, c_i, c_l, c_i, c_i, C.c_uint64, c_p, c_p],
-    "mcl_spatial_stats": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
-    "mcl_spatial_moments": [c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_spatial_perm_summary": [c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
-    # csrc/mixture.hip: the stream is a plain trailing c_p as for leiden; mixture.py passes current_stream()
+    "mcl_spatial_lattice": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_spatial_permutations": [c_p, c_i, c_l, c_i, c_i, C.c_uint64, c_p, c_s],
+    "mcl_spatial_stats": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_s],
+    "mcl_spatial_moments": [c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_spatial_perm_summary": [c_i, c_i, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_gmm_workspace_bytes": [c_l, c_i, c_i, c_i, c_i],
     "mcl_gmm_fit": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_d, c_i, c_d, c_p, c_l, c_p, c_p, c_p, c_p, c_p,
-                    c_p, c_p, c_p, c_p, c_p, c_p],
+                    c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_gmm_select": [c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
-                       c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_gmm_predict": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_gmm_mstep": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_d, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_p],
+                       c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_gmm_predict": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_gmm_mstep": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_d, c_p, c_l, c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_cluster_validity_workspace_bytes": [c_l, c_i, c_i],
-    "mcl_cluster_validity": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_p, c_l, c_p, c_p, c_p],
-    # csrc/hmrf.hip: the stream is a plain trailing c_p as for leiden; hmrf.py passes current_stream()
+    "mcl_cluster_validity": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_p, c_l, c_p, c_p, c_s],
     "mcl_hmrf_workspace_bytes": [c_l, c_i, c_i, c_i, c_i],
     "mcl_hmrf_fit": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_d, c_i, c_d, c_p, c_l,
-                     c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+                     c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
     "mcl_hmrf_estep": [c_p, c_l, c_p, c_i, c_l, c_i, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_p,
-                       c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_label_refine": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_p],
-    "mcl_edge_agreement": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p],
-    # csrc/ligrec.hip: the stream is a plain trailing c_p as for leiden; ligrec.py passes current_stream()
+                       c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_label_refine": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_p, c_s],
+    "mcl_edge_agreement": [c_p, c_i, c_l, c_p, c_p, c_p, c_i, c_p, c_s],
     "mcl_ligrec_columns": [c_i],
     "mcl_ligrec_chunk": [c_i, c_i, c_i, c_i],
     "mcl_ligrec_workspace_bytes": [c_i, c_i, c_i, c_i],
-    "mcl_ligrec_prepare": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_p],
+    "mcl_ligrec_prepare": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
     "mcl_ligrec_group_means": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_i, c_i, c_p, c_i, c_i,
-                               c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
-    "mcl_ligrec_observed": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_d, c_p, c_p, c_p, c_p, c_p],
-    "mcl_ligrec_count": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p],
-    # csrc/nhood.hip: the stream is a plain trailing c_p as for leiden; nhood.py passes current_stream()
+                               c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_ligrec_observed": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_d, c_p, c_p, c_p, c_p, c_s],
+    "mcl_ligrec_count": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_s],
     "mcl_nhood_tile_rows": [c_i, c_i],
     "mcl_nhood_staged": [c_i, c_i, c_i],
     "mcl_nhood_workspace_bytes": [c_l, c_i],
-    "mcl_nhood_counts": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    "mcl_nhood_counts": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_s],
     "mcl_cooccur_workspace_bytes": [c_l],
-    "mcl_cooccur_counts": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
-    "mcl_cooccur_scores": [c_p, c_i, c_i, c_i, c_p, c_p, c_p],
+    "mcl_cooccur_counts": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "mcl_cooccur_scores": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,

@@ -646,7 +646,7 @@ extern "C" int64_t mcl_sym_eig_workspace_bytes(int32_t S, int32_t max_m, int64_t
 
 extern "C" int mcl_sym_eig_top(double* a, const int64_t* a_offsets, const int32_t* m, int32_t S, int32_t max_m,
                                int64_t sum_m, int32_t k, int32_t stages, double* evals, double* evecs,
-                               const int64_t* evec_offsets, double* cert, void* work, void* stream) {
+                               const int64_t* evec_offsets, double* cert, void* work, mcl_stream_t stream) {
   if (!a || !a_offsets || !m || !evals || !evecs || !evec_offsets || !cert || !work) return MCL_EINVAL;
   if (stages < 1 || stages > 7) return MCL_EINVAL;
   const int rc = eig_check_sizes(S, max_m, sum_m, k);

@@ -307,7 +307,7 @@ extern "C" int mcl_hmrf_fit(const double* z, int64_t ld, const int64_t* offsets,
                             double tol, int32_t max_iter, double reg_covar, void* work, int64_t work_bytes,
                             int32_t* labels_all, double* weights_all, double* means_all, double* covariances_all,
                             double* precisions_cholesky_all, double* lower_bound_all, double* score_all,
-                            int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all, void* stream) {
+                            int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all, mcl_stream_t stream) {
   if (!z || !offsets || !k || !init_labels || !nbr || !w || !beta || !work || !labels_all || !weights_all || !means_all ||
       !covariances_all || !precisions_cholesky_all || !lower_bound_all || !score_all || !n_iter_all || !converged_all ||
       !status_all)
@@ -332,7 +332,7 @@ extern "C" int mcl_hmrf_estep(const double* z, int64_t ld, const int64_t* offset
                               const double* means, const double* precisions_cholesky, const double* resp_prev,
                               const int32_t* nbr, const double* w, int32_t kw, const double* beta, double* field,
                               double* log_resp, double* resp, int32_t* labels, double* log_prob_norm,
-                              double* log_prior_norm, double* score, int32_t* status, void* stream) {
+                              double* log_prior_norm, double* score, int32_t* status, mcl_stream_t stream) {
   if (!z || !offsets || !k || !weights || !means || !precisions_cholesky || !resp_prev || !nbr || !w || !beta || !field ||
       !log_resp || !resp || !labels || !log_prob_norm || !log_prior_norm || !score || !status)
     return MCL_EINVAL;
@@ -349,7 +349,7 @@ extern "C" int mcl_hmrf_estep(const double* z, int64_t ld, const int64_t* offset
 }
 
 extern "C" int mcl_label_refine(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels, const int32_t* nbr,
-                                const double* w, int32_t kw, int32_t* labels_out, int32_t* changed, void* stream) {
+                                const double* w, int32_t kw, int32_t* labels_out, int32_t* changed, mcl_stream_t stream) {
   if (!offsets || !labels || !nbr || !w || !labels_out || !changed) return MCL_EINVAL;
   if (S < 1 || rows < 1 || kw < 1 || labels == labels_out) return MCL_EINVAL;
   if (kw > HM_MAX_KW || S > 65535) return MCL_EUNSUPPORTED;
@@ -362,7 +362,7 @@ extern "C" int mcl_label_refine(const int64_t* offsets, int32_t S, int64_t rows,
 }
 
 extern "C" int mcl_edge_agreement(const int64_t* offsets, int32_t S, int64_t rows, const int32_t* labels,
-                                  const int32_t* nbr, const double* w, int32_t kw, double* sums, void* stream) {
+                                  const int32_t* nbr, const double* w, int32_t kw, double* sums, mcl_stream_t stream) {
   if (!offsets || !labels || !nbr || !w || !sums) return MCL_EINVAL;
   if (S < 1 || rows < 1 || kw < 1) return MCL_EINVAL;
   if (kw > HM_MAX_KW || S > 65535) return MCL_EUNSUPPORTED;

@@ -960,7 +960,7 @@ int64_t mcl_leiden_workspace_bytes(int64_t rows, int64_t nnz_total, int32_t S, i
 
 int mcl_leiden_init(const int64_t* indptr, const int32_t* indices, const double* data, const int64_t* offsets,
                     const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution,
-                    const int32_t* partition, const int32_t* active, void* work, void* stream) {
+                    const int32_t* partition, const int32_t* active, void* work, mcl_stream_t stream) {
   ld_args A;
   const int rc = ld_make(indptr, indices, offsets, nnz_offsets, S, rows, max_n, nnz_total, resolution, 0, work, &A);
   if (rc != MCL_OK) return rc;
@@ -979,7 +979,7 @@ int mcl_leiden_init(const int64_t* indptr, const int32_t* indices, const double*
 int mcl_leiden_move_sweeps(int32_t count, int32_t level, int32_t n_cur, int32_t long_rows, int32_t max_sweeps,
                            const int64_t* indptr, const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets,
                            int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total, double resolution, void* work,
-                           void* stream) {
+                           mcl_stream_t stream) {
   ld_args A;
   const int rc = ld_make(indptr, indices, offsets, nnz_offsets, S, rows, max_n, nnz_total, resolution, level, work, &A);
   if (rc != MCL_OK) return rc;
@@ -1001,7 +1001,7 @@ int mcl_leiden_move_sweeps(int32_t count, int32_t level, int32_t n_cur, int32_t 
 int mcl_leiden_refine_rounds(int32_t begin, int32_t count, int32_t level, int32_t n_cur, int32_t long_rows,
                              int32_t max_rounds, const int64_t* indptr, const int32_t* indices, const int64_t* offsets,
                              const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n, int64_t nnz_total,
-                             double resolution, void* work, void* stream) {
+                             double resolution, void* work, mcl_stream_t stream) {
   ld_args A;
   const int rc = ld_make(indptr, indices, offsets, nnz_offsets, S, rows, max_n, nnz_total, resolution, level, work, &A);
   if (rc != MCL_OK) return rc;
@@ -1028,7 +1028,7 @@ int mcl_leiden_refine_rounds(int32_t begin, int32_t count, int32_t level, int32_
 
 int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const int64_t* indptr, const int32_t* indices,
                          const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows, int32_t max_n,
-                         int64_t nnz_total, double resolution, void* work, void* stream) {
+                         int64_t nnz_total, double resolution, void* work, mcl_stream_t stream) {
   ld_args A;
   const int rc = ld_make(indptr, indices, offsets, nnz_offsets, S, rows, max_n, nnz_total, resolution, level, work, &A);
   if (rc != MCL_OK) return rc;
@@ -1052,7 +1052,7 @@ int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const
 int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* active, const int64_t* indptr,
                       const int32_t* indices, const int64_t* offsets, const int64_t* nnz_offsets, int32_t S, int32_t rows,
                       int32_t max_n, int64_t nnz_total, void* work, int32_t* canonical, int32_t* labels, int32_t* n_clusters,
-                      void* stream) {
+                      mcl_stream_t stream) {
   ld_args A;
   const int rc = ld_make(indptr, indices, offsets, nnz_offsets, S, rows, max_n, nnz_total, 1.0, 0, work, &A);
   if (rc != MCL_OK) return rc;

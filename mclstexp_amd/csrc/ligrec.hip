@@ -451,7 +451,7 @@ extern "C" int64_t mcl_ligrec_workspace_bytes(int32_t S, int32_t kmax, int32_t U
 
 extern "C" int mcl_ligrec_prepare(const int64_t* offsets, const int32_t* labels, const int32_t* k, int32_t S, int64_t rows,
                                   int32_t max_n, int32_t kmax, int32_t* order, int32_t* start, int64_t* kept_offsets,
-                                  int32_t* status, void* stream) {
+                                  int32_t* status, mcl_stream_t stream) {
   if (!offsets || !labels || !k || !order || !start || !kept_offsets || !status) return MCL_EINVAL;
   if (!lr_shape_ok(S, rows, max_n, kmax)) return MCL_EINVAL;
   if (!lr_limits_ok(max_n, kmax)) return MCL_EUNSUPPORTED;
@@ -471,7 +471,7 @@ extern "C" int mcl_ligrec_group_means(const void* x, int64_t ld, int32_t dtype, 
                                       const int32_t* k, int32_t S, int64_t rows, int32_t G, int32_t max_n, int32_t kmax,
                                       const int32_t* used, int32_t U, int32_t column_mask, const void* table,
                                       int32_t n_perms, int32_t p0, int32_t pc, int32_t chunk, double* sum, int32_t* nnz,
-                                      double* mean, double* frac, double* perm_means, int32_t* status, void* stream) {
+                                      double* mean, double* frac, double* perm_means, int32_t* status, mcl_stream_t stream) {
   if (!x || !offsets || !kept_offsets || !order || !start || !k || !used || !status) return MCL_EINVAL;
   if (!lr_shape_ok(S, rows, max_n, kmax) || G < 1 || U < 1 || U > G || ld < G || (dtype != 0 && dtype != 1) ||
       (column_mask & ~0x116) || !column_mask)
@@ -505,7 +505,7 @@ static bool lr_cells_ok(int32_t S, int32_t I, int32_t kmax) {
 extern "C" int mcl_ligrec_observed(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const int32_t* start,
                                    const double* sum, const int32_t* nnz, const double* mean,
                                    const int32_t* member_offsets, const int32_t* members, double threshold, int32_t* pairs,
-                                   double* means, int32_t* defined, int32_t* count, void* stream) {
+                                   double* means, int32_t* defined, int32_t* count, mcl_stream_t stream) {
   if (!k || !start || !sum || !nnz || !mean || !member_offsets || !members || !pairs || !means || !defined || !count)
     return MCL_EINVAL;
   if (U < 1 || !(threshold >= 0.0 && threshold <= 1.0) || S < 1 || I < 1 || kmax < 1) return MCL_EINVAL;
@@ -519,7 +519,7 @@ extern "C" int mcl_ligrec_observed(int32_t S, int32_t I, int32_t kmax, int32_t U
 
 extern "C" int mcl_ligrec_count(int32_t S, int32_t I, int32_t kmax, int32_t U, const int32_t* k, const double* mean,
                                 const int32_t* pairs, const double* perm_means, int32_t chunk, int32_t pc, int32_t* count,
-                                void* stream) {
+                                mcl_stream_t stream) {
   if (!k || !mean || !pairs || !perm_means || !count) return MCL_EINVAL;
   if (U < 1 || chunk < 1 || pc < 1 || pc > chunk || S < 1 || I < 1 || kmax < 1) return MCL_EINVAL;
   if (!lr_cells_ok(S, I, kmax) || U > LR_MAX_G || chunk > LR_MAX_PERMS) return MCL_EUNSUPPORTED;

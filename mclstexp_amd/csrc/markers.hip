@@ -570,7 +570,7 @@ extern "C" int mcl_marker_stats(const void* x, int64_t ld, int32_t dtype, const 
                                 const int32_t* k, int32_t S, int64_t rows, int32_t G, int32_t max_n, int32_t kmax,
                                 int64_t groups_total, void* work, int32_t* group_sizes, int32_t* n_valid, double* mean_g,
                                 double* var_g, double* mean_r, double* var_r, double* pts_g, double* pts_r,
-                                int32_t* nnz_g, int32_t* nnz_r, int32_t* status, void* stream) {
+                                int32_t* nnz_g, int32_t* nnz_r, int32_t* status, mcl_stream_t stream) {
   if (!x || !offsets || !labels || !k || !work || !group_sizes || !n_valid || !mean_g || !var_g || !mean_r || !var_r ||
       !pts_g || !pts_r || !nnz_g || !nnz_r || !status)
     return MCL_EINVAL;
@@ -597,7 +597,7 @@ extern "C" int mcl_marker_stats(const void* x, int64_t ld, int32_t dtype, const 
 
 extern "C" int mcl_marker_rank_sums(const void* x, int64_t ld, int32_t dtype, const int32_t* labels, int32_t S,
                                     int64_t rows, int32_t G, int32_t max_n, int32_t kmax, int64_t groups_total, void* work,
-                                    int64_t* rank_sums2, int64_t* tie_terms, void* stream) {
+                                    int64_t* rank_sums2, int64_t* tie_terms, mcl_stream_t stream) {
   if (!x || !labels || !work || !rank_sums2 || !tie_terms) return MCL_EINVAL;
   if (!mk_shape_ok(S, rows, G, max_n, kmax, groups_total) || ld < G || (dtype != 0 && dtype != 1)) return MCL_EINVAL;
   const hipStream_t st = static_cast<hipStream_t>(stream);
@@ -610,7 +610,7 @@ extern "C" int mcl_marker_test(int32_t method, int32_t tie_correct, int32_t S, i
                                int64_t groups_total, const void* work, const int32_t* group_sizes, const double* mean_g,
                                const double* var_g, const double* mean_r, const double* var_r, const int64_t* rank_sums2,
                                const int64_t* tie_terms, double* scores, double* pvals, double* neglog10_pvals,
-                               double* logfoldchanges, void* stream) {
+                               double* logfoldchanges, mcl_stream_t stream) {
   if (!work || !group_sizes || !mean_g || !var_g || !mean_r || !var_r || !scores || !pvals || !neglog10_pvals ||
       !logfoldchanges)
     return MCL_EINVAL;
@@ -631,7 +631,7 @@ extern "C" int mcl_marker_rank_adjust(int32_t S, int64_t rows, int32_t G, int32_
                                       const double* pvals, const double* neglog10_pvals, const double* logfoldchanges,
                                       double* pvals_adj, int64_t* names, double* top_scores, double* top_pvals,
                                       double* top_pvals_adj, double* top_neglog10_pvals, double* top_logfoldchanges,
-                                      void* stream) {
+                                      mcl_stream_t stream) {
   if (!work || !scores || !pvals || !neglog10_pvals || !logfoldchanges || !pvals_adj || !names || !top_scores ||
       !top_pvals || !top_pvals_adj || !top_neglog10_pvals || !top_logfoldchanges)
     return MCL_EINVAL;

@@ -485,7 +485,7 @@ extern "C" int mcl_gmm_fit(const double* z, int64_t ld, const int64_t* offsets, 
                            int64_t work_bytes, int32_t* labels_all, double* weights_all, double* means_all,
                            double* covariances_all, double* precisions_cholesky_all, double* lower_bound_all,
                            double* score_all, int32_t* n_iter_all, int32_t* converged_all, int32_t* status_all,
-                           void* stream) {
+                           mcl_stream_t stream) {
   if (!z || !offsets || !k || !init_labels || !work || !labels_all || !weights_all || !means_all || !covariances_all ||
       !precisions_cholesky_all || !lower_bound_all || !score_all || !n_iter_all || !converged_all || !status_all)
     return MCL_EINVAL;
@@ -512,7 +512,7 @@ extern "C" int mcl_gmm_select(const int64_t* offsets, int32_t S, int64_t rows, i
                               const int32_t* converged_all, const int32_t* status_all, int32_t* labels, double* resp,
                               double* weights, double* means, double* covariances, double* precisions_cholesky,
                               double* lower_bound, int32_t* n_iter, int32_t* converged, int32_t* status, double* bic,
-                              double* aic, int32_t* restart, void* stream) {
+                              double* aic, int32_t* restart, mcl_stream_t stream) {
   if (!offsets || !k || !work || !labels_all || !weights_all || !means_all || !covariances_all ||
       !precisions_cholesky_all || !lower_bound_all || !score_all || !n_iter_all || !converged_all || !status_all ||
       !labels || !resp || !weights || !means || !covariances || !precisions_cholesky || !lower_bound || !n_iter ||
@@ -535,7 +535,7 @@ extern "C" int mcl_gmm_select(const int64_t* offsets, int32_t S, int64_t rows, i
 extern "C" int mcl_gmm_predict(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                                const int32_t* k, int32_t k_max, int32_t covariance_type, const double* weights,
                                const double* means, const double* precisions_cholesky, double* log_prob_norm,
-                               double* log_resp, double* resp, int32_t* labels, double* score, void* stream) {
+                               double* log_resp, double* resp, int32_t* labels, double* score, mcl_stream_t stream) {
   if (!z || !offsets || !k || !weights || !means || !precisions_cholesky || !log_prob_norm || !log_resp || !resp ||
       !labels || !score)
     return MCL_EINVAL;
@@ -552,7 +552,7 @@ extern "C" int mcl_gmm_predict(const double* z, int64_t ld, const int64_t* offse
 extern "C" int mcl_gmm_mstep(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                              const int32_t* k, int32_t k_max, int32_t covariance_type, const double* log_resp,
                              double reg_covar, void* work, int64_t work_bytes, double* weights, double* means,
-                             double* covariances, double* precisions_cholesky, int32_t* status, void* stream) {
+                             double* covariances, double* precisions_cholesky, int32_t* status, mcl_stream_t stream) {
   if (!z || !offsets || !k || !log_resp || !work || !weights || !means || !covariances || !precisions_cholesky || !status)
     return MCL_EINVAL;
   if (!gm_shape_ok(S, rows, D, k_max, covariance_type) || ld < D || !(reg_covar >= 0.0)) return MCL_EINVAL;
@@ -573,7 +573,7 @@ extern "C" int64_t mcl_cluster_validity_workspace_bytes(int64_t rows, int32_t S,
 
 extern "C" int mcl_cluster_validity(const double* z, int64_t ld, const int64_t* offsets, int32_t S, int64_t rows, int32_t D,
                                     const int32_t* labels, void* work, int64_t work_bytes, double* silhouette,
-                                    double* scores, void* stream) {
+                                    double* scores, mcl_stream_t stream) {
   if (!z || !offsets || !labels || !work || !silhouette || !scores) return MCL_EINVAL;
   if (S < 1 || rows < 1 || D < 1 || ld < D) return MCL_EINVAL;
   if (D > GM_MAX || S > 65535) return MCL_EUNSUPPORTED;

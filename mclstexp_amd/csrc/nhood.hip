@@ -354,7 +354,7 @@ extern "C" int mcl_nhood_counts(const int64_t* offsets, const int64_t* kept_offs
                                 const int32_t* start, const int32_t* k, int32_t S, int64_t rows, int32_t max_n,
                                 int32_t kmax, const int32_t* nbr, const double* w, int32_t kw, const void* table,
                                 int32_t n_perms, void* work, int32_t* count, int64_t* stats, int32_t* status,
-                                void* stream) {
+                                mcl_stream_t stream) {
   if (!offsets || !kept_offsets || !order || !start || !k || !nbr || !w || !work || !count || !status) return MCL_EINVAL;
   if (!nh_shape_ok(S, rows, max_n, kmax) || kw < 1 || n_perms < 0 || (table && (!stats || n_perms < 1)) ||
       (!table && n_perms != 0))
@@ -410,7 +410,7 @@ extern "C" int64_t mcl_cooccur_workspace_bytes(int64_t rows) {
 extern "C" int mcl_cooccur_counts(const double* coords, const int64_t* offsets, const int32_t* order, const int32_t* start,
                                   const int32_t* k, int32_t S, int64_t rows, int32_t max_n, int32_t kmax,
                                   const double* radii_sq, int32_t T, void* work, int32_t* pairs, int32_t* status,
-                                  void* stream) {
+                                  mcl_stream_t stream) {
   if (!coords || !offsets || !order || !start || !k || !radii_sq || !work || !pairs || !status) return MCL_EINVAL;
   if (!nh_shape_ok(S, rows, max_n, kmax) || T < 1) return MCL_EINVAL;
   if (T > NH_MAX_T || !nh_limits_ok(S, max_n, kmax, T)) return MCL_EUNSUPPORTED;
@@ -435,7 +435,7 @@ extern "C" int mcl_cooccur_counts(const double* coords, const int64_t* offsets, 
 }
 
 extern "C" int mcl_cooccur_scores(const int32_t* k, int32_t S, int32_t kmax, int32_t T, int32_t* pairs, double* occ,
-                                  void* stream) {
+                                  mcl_stream_t stream) {
   if (!k || !pairs || !occ || S < 1 || kmax < 1 || T < 1) return MCL_EINVAL;
   if (T > NH_MAX_T || S > NH_MAX_S || kmax > NH_MAX_K || (long long)S * T * kmax * kmax > NH_MAX_TOTAL)
     return MCL_EUNSUPPORTED;

@@ -630,7 +630,7 @@ extern "C" int32_t mcl_spatial_columns(int32_t n) { return (n < 2 || n > SP_MAX_
 extern "C" int mcl_spatial_lattice(const int32_t* knn_indices, const double* knn_distances, const int64_t* offsets,
                                    int32_t S, int64_t rows, int32_t max_n, int32_t k, int32_t prune,
                                    int32_t row_standardise, int32_t given, void* work, int32_t* nbr, double* w,
-                                   int32_t* deg, double* consts, int32_t* status, void* stream) {
+                                   int32_t* deg, double* consts, int32_t* status, mcl_stream_t stream) {
   if (!offsets || !work || !nbr || !w || !deg || !consts || !status) return MCL_EINVAL;
   if (!given && (!knn_indices || !knn_distances)) return MCL_EINVAL;
   if (!sp_shape_ok(S, rows, max_n) || k < 1 || k > SP_MAX_K || prune < 0 || prune > 2) return MCL_EINVAL;
@@ -656,7 +656,7 @@ extern "C" int mcl_spatial_lattice(const int32_t* knn_indices, const double* knn
 }
 
 extern "C" int mcl_spatial_permutations(const int64_t* offsets, int32_t S, int64_t rows, int32_t max_n, int32_t n_perms,
-                                        uint64_t seed, void* work, void* stream) {
+                                        uint64_t seed, void* work, mcl_stream_t stream) {
   if (!offsets || !work || !sp_shape_ok(S, rows, max_n) || n_perms < 1 || n_perms > SP_MAX_PERMS) return MCL_EINVAL;
   const size_t lds = (size_t)sp_pow2ceil(max_n) * 8;
   static mcl_device_once attr_once;
@@ -675,7 +675,7 @@ extern "C" int mcl_spatial_permutations(const int64_t* offsets, int32_t S, int64
 extern "C" int mcl_spatial_stats(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows,
                                  int32_t G, int32_t max_n, int32_t k, int32_t column_mask, const int32_t* nbr,
                                  const double* w, const double* consts, const void* table, int32_t n_perms, double* mean,
-                                 double* den, double* stat, int32_t* status, void* stream) {
+                                 double* den, double* stat, int32_t* status, mcl_stream_t stream) {
   if (!x || !offsets || !nbr || !w || !consts || !stat || !status) return MCL_EINVAL;
   if (!sp_shape_ok(S, rows, max_n) || G < 1 || G > SP_MAX_G || ld < G || (dtype != 0 && dtype != 1) || k < 1 ||
       k > SP_MAX_K || n_perms < 1 || n_perms > SP_MAX_PERMS || (column_mask & ~0x7E) || !column_mask)
@@ -692,7 +692,7 @@ extern "C" int mcl_spatial_stats(const void* x, int64_t ld, int32_t dtype, const
 extern "C" int mcl_spatial_moments(const int64_t* offsets, int32_t S, int64_t rows, int32_t G, int32_t max_n,
                                    const double* consts, const double* stat, int32_t two_tailed, int32_t* prank,
                                    double* scratch, double* z_norm, double* pval_norm, double* neglog10_pval_norm,
-                                   double* pval_norm_adj, void* stream) {
+                                   double* pval_norm_adj, mcl_stream_t stream) {
   if (!offsets || !consts || !stat || !prank || !scratch || !z_norm || !pval_norm || !neglog10_pval_norm || !pval_norm_adj)
     return MCL_EINVAL;
   if (!sp_shape_ok(S, rows, max_n) || G < 1 || G > SP_MAX_G || 2 * S > SP_MAX_S) return MCL_EINVAL;
@@ -712,7 +712,7 @@ extern "C" int mcl_spatial_moments(const int64_t* offsets, int32_t S, int64_t ro
 
 extern "C" int mcl_spatial_perm_summary(int32_t S, int32_t G, int32_t n_perms, const double* stat, const double* sims,
                                         int32_t two_tailed, int32_t* count, double* pval_sim, double* pval_z_sim,
-                                        double* mean_sim, double* var_sim, void* stream) {
+                                        double* mean_sim, double* var_sim, mcl_stream_t stream) {
   if (!stat || !sims || !count || !pval_sim || !pval_z_sim || !mean_sim || !var_sim) return MCL_EINVAL;
   if (S < 1 || S > SP_MAX_S || G < 1 || G > SP_MAX_G || n_perms < 1 || n_perms > SP_MAX_PERMS) return MCL_EINVAL;
   MCL_CLEAR_ERROR();

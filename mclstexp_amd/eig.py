@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, upload
-from ._lib import call, current_stream
+from ._lib import call
 
 MAX_M = 4096         # order of a matrix (csrc/eig.hip: a column of Z sits in LDS)
 MAX_K = 64           # eigenpairs per matrix
@@ -58,8 +58,7 @@ def solve(a: Tensor, a_offsets: np.ndarray, sizes: np.ndarray, k: int, evec_offs
     work = e((int(call("mcl_sym_eig_workspace_bytes", S, max_m, sum_m, k)) // 8 + 1,), torch.float64)
     aoff_d = upload(a_offsets, dev) if a_offsets_d is None else a_offsets_d
     eoff_d, m_d = upload(eoff, dev), upload(m, dev)
-    call("mcl_sym_eig_top", a, aoff_d, m_d, S, max_m, sum_m, k, ALL_STAGES, values, vectors, eoff_d, cert, work,
-         current_stream())
+    call("mcl_sym_eig_top", a, aoff_d, m_d, S, max_m, sum_m, k, ALL_STAGES, values, vectors, eoff_d, cert, work)
     return {"values": values, "vectors_flat": vectors, "evec_offsets": eoff_d, "evec_offsets_host": eoff,
             "certificate": cert, "sizes": m}
 

@@ -38,7 +38,7 @@ import torch
 
 from . import cluster, mixture
 from ._arrays import ArrayLike, Tensor, device, empty, matrix, stack_rows, upload
-from ._lib import call, current_stream
+from ._lib import call
 
 MAX_DIM = cluster.MAX_DIM          # D <= 64 and K <= 64 (csrc/hmrf.hip)
 MAX_ROWS = 16384                   # per slide: the lattice's
@@ -134,7 +134,7 @@ def _n_rows(labels) -> int:
 
 def _edge_sums(lab: Tensor, nbr: Tensor, w: Tensor, kw: int, off_d: Tensor, S: int, rows: int) -> Tensor:
     sums = torch.empty((S, 2), device=lab.device, dtype=torch.float64)
-    call("mcl_edge_agreement", off_d, S, rows, lab, nbr, w, kw, sums, current_stream())
+    call("mcl_edge_agreement", off_d, S, rows, lab, nbr, w, kw, sums)
     return sums
 
 
@@ -205,10 +205,10 @@ def hmrf(z: ArrayLike, graph: Dict[str, object], k: Union[int, Sequence[int]], b
     alls = [res[n] for n in ("labels_all", "weights_all", "means_all", "covariances_all", "precisions_cholesky_all",
                              "lower_bound_all", "score_all", "n_iter_all", "converged_all", "status_all")]
     call("mcl_hmrf_fit", zd, zd.stride(0), off_d, S, rows, D, ks_d, k_max, R, code, init, nbr, w, kw, beta_d, float(tol),
-         int(max_iter), float(reg_covar), work, wb, *alls, current_stream())
+         int(max_iter), float(reg_covar), work, wb, *alls)
     call("mcl_gmm_select", off_d, S, rows, D, ks_d, k_max, R, code, work, wb, *alls, res["labels"], res["resp"],
          res["weights"], res["means"], res["covariances"], res["precisions_cholesky"], res["lower_bound"], res["n_iter"],
-         res["converged"], res["status"], res["bic"], res["aic"], res["restart"], current_stream())
+         res["converged"], res["status"], res["bic"], res["aic"], res["restart"])
     start = torch.repeat_interleave(res["restart"].long(), upload(seg, dev))          # the winning start of every row
     res["field"] = field_all[start, torch.arange(rows, device=dev)]
     res["edge_agreement"] = _ratio(_edge_sums(res["labels"], nbr, w, kw, off_d, S, rows))
@@ -266,7 +266,7 @@ def estep(z: ArrayLike, model: Dict[str, object], graph: Dict[str, object], resp
     res["log_resp"].fill_(float("-inf"))
     call("mcl_hmrf_estep", zd, zd.stride(0), upload(off, dev), S, rows, D, upload(ks, dev), k_max, code, wts, mu, pc, q, nbr,
          w, kw, upload(bs, dev), res["field"], res["log_resp"], res["resp"], res["labels"], res["log_prob_norm"],
-         res["log_prior_norm"], res["score"], res["status"], current_stream())
+         res["log_prior_norm"], res["score"], res["status"])
     return res
 
 
@@ -292,7 +292,7 @@ def refine_labels(labels: ArrayLike, graph: Dict[str, object], n_iter: int = 1) 
     cnt = torch.empty((S,), device=dev, dtype=torch.int32)
     for it in range(int(n_iter)):
         out = torch.empty_like(lab)
-        call("mcl_label_refine", off_d, S, rows, lab, nbr, w, kw, out, cnt, current_stream())
+        call("mcl_label_refine", off_d, S, rows, lab, nbr, w, kw, out, cnt)
         changed[it] = cnt.cpu().numpy()
         lab = out
         if not changed[it].any():

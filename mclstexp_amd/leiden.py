@@ -38,9 +38,8 @@ import numpy as np
 import torch
 
 from . import _arrays, neighbors, umap
-from ._arrays import ArrayLike, Tensor, device, empty, upload
-from ._lib import call, current_stream
-from .neighbors import _dense
+from ._arrays import ArrayLike, Tensor, dense, device, empty, upload
+from ._lib import call
 from .umap import _check_graph
 
 MAX_ROWS = 16384         # csrc/leiden.hip
@@ -119,9 +118,9 @@ class _Run:
         dev = self.dev = device("leiden")
         e = empty(dev)
         S, rows, total = self.S, self.rows, self.total
-        self.indptr = _dense(graph["indptr"], "indptr", (rows + S,), torch.int64, dev)
-        self.indices = _dense(graph["indices"], "indices", (total,), torch.int32, dev) if total else e((1,), torch.int32)
-        self.data = _dense(graph["data"], "data", (total,), torch.float64, dev) if total else e((1,), torch.float64)
+        self.indptr = dense(graph["indptr"], "indptr", (rows + S,), torch.int64, dev)
+        self.indices = dense(graph["indices"], "indices", (total,), torch.int32, dev) if total else e((1,), torch.int32)
+        self.data = dense(graph["data"], "data", (total,), torch.float64, dev) if total else e((1,), torch.float64)
         self.off_d, self.nnz_off_d = upload(off, dev), upload(nnz_off, dev)
         nbytes = int(call("mcl_leiden_workspace_bytes", rows, total, S, self.max_n))
         self.work = e((nbytes // 8 + 1,), torch.int64)
@@ -141,7 +140,7 @@ class _Run:
 
     def init(self, partition: Optional[Tensor], active: Optional[Tensor]) -> np.ndarray:
         call("mcl_leiden_init", self.indptr, self.indices, self.data, self.off_d, self.nnz_off_d, self.S, self.rows, self.max_n,
-             self.total, self.gamma, partition, active, self.work, current_stream())
+             self.total, self.gamma, partition, active, self.work)
         return self.state()
 
     def _sizes(self, st: np.ndarray, level: int):
@@ -154,7 +153,7 @@ class _Run:
         n_cur, long_rows = self._sizes(st, level)
         while True:
             call("mcl_leiden_move_sweeps", BATCH, level, n_cur, long_rows, self.max_sweeps, *self.graph_args, self.gamma,
-                 self.work, current_stream())
+                 self.work)
             st = self.state()
             if ((st["f"][:, F_MOVE_DONE] != 0) | (st["f"][:, F_FINISHED] != 0)).all():
                 return st
@@ -164,7 +163,7 @@ class _Run:
         begin = 1
         while True:
             call("mcl_leiden_refine_rounds", begin, BATCH, level, n_cur, long_rows, self.max_sweeps, *self.graph_args,
-                 self.gamma, self.work, current_stream())
+                 self.gamma, self.work)
             begin = 0
             st = self.state()
             if ((st["f"][:, F_REF_DONE] != 0) | (st["f"][:, F_FINISHED] != 0)).all():
@@ -172,11 +171,11 @@ class _Run:
 
     def aggregate(self, st: np.ndarray, level: int) -> np.ndarray:
         n_cur, _ = self._sizes(st, level)
-        call("mcl_leiden_aggregate", level, n_cur, self.max_levels, *self.graph_args, self.gamma, self.work, current_stream())
+        call("mcl_leiden_aggregate", level, n_cur, self.max_levels, *self.graph_args, self.gamma, self.work)
         return self.state()
 
     def finish(self, source: int, final: int, active, canon: Tensor, labels=None, n_clusters=None) -> None:
-        call("mcl_leiden_finish", source, final, active, *self.graph_args, self.work, canon, labels, n_clusters, current_stream())
+        call("mcl_leiden_finish", source, final, active, *self.graph_args, self.work, canon, labels, n_clusters)
 
     def iteration(self, partition: Optional[Tensor], active: Tensor, canon: Tensor) -> np.ndarray:
         """One pass over the levels for the active slides from ``partition``; their canonical ids land in ``canon``."""

@@ -47,8 +47,9 @@ import numpy as np
 import torch
 
 from . import markers, spatial
-from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, stack_rows, upload
-from ._lib import call, current_stream
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, nanmean,
+                      stack_rows, upload)
+from ._lib import call
 
 MAX_ROWS = 16384         # csrc/ligrec.hip: the uint16 permutation tables of csrc/spatial.hip
 MAX_GROUPS = 255
@@ -201,15 +202,14 @@ def ligrec_device(x: ArrayLike, labels, interactions, offsets: Optional[Sequence
     off_d, k_d, used_d = upload(off, dev), upload(kk, dev), upload(used, dev)
     moff_d, mem_d = upload(moff, dev), upload(members, dev)
     order, start, koff, status = e((rows,), i32), e((S, kmax + 1), i32), e((S + 1,), i64), e((S, 4), i32)
-    st = current_stream()
-    call("mcl_ligrec_prepare", off_d, lab_d, k_d, S, rows, max_n, kmax, order, start, koff, status, st)
+    call("mcl_ligrec_prepare", off_d, lab_d, k_d, S, rows, max_n, kmax, order, start, koff, status)
     gsum, gmean, gfrac, nnz = e((S, kmax, U), f64), e((S, kmax, U), f64), e((S, kmax, U), f64), e((S, kmax, U), i32)
     call("mcl_ligrec_group_means", xd, ld, code, off_d, koff, order, start, k_d, S, rows, G, max_n, kmax, used_d, U, mask,
-         None, 1, 0, 1, 1, gsum, nnz, gmean, gfrac, None, status, st)
+         None, 1, 0, 1, 1, gsum, nnz, gmean, gfrac, None, status)
     pairs = e((S, I, 2), i32)
     means, defined, count = e((S, I, kmax, kmax), f64), e((S, I, kmax, kmax), i32), e((S, I, kmax, kmax), i32)
     call("mcl_ligrec_observed", S, I, kmax, U, k_d, start, gsum, nnz, gmean, moff_d, mem_d, threshold, pairs, means,
-         defined, count, st)
+         defined, count)
     out = {"means": means, "defined": defined, "count": count, "pairs": pairs, "sum": gsum, "nnz": nnz, "group_means": gmean,
            "group_frac": gfrac, "order": order, "start": start, "kept_offsets": koff, "status": status, "offsets": off,
            "k": kk, "used": used, "sides": sides, "n_perms": P, "threshold": threshold}
@@ -217,7 +217,7 @@ def ligrec_device(x: ArrayLike, labels, interactions, offsets: Optional[Sequence
         work = e((int(call("mcl_spatial_workspace_bytes", rows, 0, P)) // 8 + 1,), f64)
         table = work.view(torch.int16)[:P * rows]
         if host_table is None:
-            call("mcl_spatial_permutations", koff, S, rows, max_n, P, seed, work, st)
+            call("mcl_spatial_permutations", koff, S, rows, max_n, P, seed, work)
         elif host_table.size:
             table[:host_table.size].copy_(torch.from_numpy(host_table))
         chunk = int(call("mcl_ligrec_chunk", S, kmax, U, P))
@@ -225,8 +225,8 @@ def ligrec_device(x: ArrayLike, labels, interactions, offsets: Optional[Sequence
         for p0 in range(0, P, chunk):                          # enqueued back to back: nothing synchronises in between
             pc = min(chunk, P - p0)
             call("mcl_ligrec_group_means", xd, ld, code, off_d, koff, order, start, k_d, S, rows, G, max_n, kmax, used_d, U,
-                 mask, work, P, p0, pc, chunk, None, None, None, None, pm, status, st)
-            call("mcl_ligrec_count", S, I, kmax, U, k_d, gmean, pairs, pm, chunk, pc, count, st)
+                 mask, work, P, p0, pc, chunk, None, None, None, None, pm, status)
+            call("mcl_ligrec_count", S, I, kmax, U, k_d, gmean, pairs, pm, chunk, pc, count)
         out.update({"table": table, "workspace": work, "chunk": chunk})
     bad = status.cpu().numpy()                                  # the one synchronisation
     for col, what in ((0, "offsets or a group count the device refuses"), (1, "group ids outside -1 .. k - 1"),
@@ -321,11 +321,6 @@ def significant(r: Dict[str, object], alpha: float, adjusted: bool) -> np.ndarra
         return np.isfinite(p) & (p < alpha)
 
 
-def _nanmean(v) -> float:
-    v = np.asarray(v, dtype=np.float64)
-    return float(v[np.isfinite(v)].mean()) if np.isfinite(v).any() else float("nan")
-
-
 def interaction_recovery(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike], labels: Sequence[Sequence], interactions,
                          alpha: float = 0.05, **kw) -> Dict[str, object]:
     """Do the predicted values call the interactions the measured ones call?  Both matrices are tested under the same
@@ -356,7 +351,7 @@ def interaction_recovery(preds: Sequence[ArrayLike], trues: Sequence[ArrayLike],
         cols["precision"].append(o / int(sa.sum()) if sa.any() else float("nan"))
         cols["recall"].append(o / int(sb.sum()) if sb.any() else float("nan"))
     out = {key: np.asarray(v) for key, v in cols.items()}
-    out.update({f"mean_{key}": _nanmean(out[key]) for key in ("pearson", "overlap", "jaccard", "precision", "recall")})
+    out.update({f"mean_{key}": nanmean(out[key]) for key in ("pearson", "overlap", "jaccard", "precision", "recall")})
     out.update({"alpha": float(alpha), "adjusted": adjusted, "pred": rp, "true": rt})
     return out
 

@@ -39,7 +39,7 @@ import torch
 from . import cluster
 from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, stack_rows,
                       upload, validate_offsets)
-from ._lib import call, current_stream
+from ._lib import call
 
 MAX_ROWS = 16384         # csrc/markers.hip: a column's keys and group bytes sit in LDS
 MAX_GROUPS = 255
@@ -146,19 +146,18 @@ def rank_genes_groups_device(x: ArrayLike, labels, offsets: Optional[Sequence[in
     gsize, nvalid, status = e((KT,), i32), e((S,), i32), e((S, 2), i32)
     mg, vg, mr, vr, pg, pr = (e((KT, G), f64) for _ in range(6))
     zg, zr = e((KT, G), i32), e((KT, G), i32)
-    st = current_stream()
     call("mcl_marker_stats", xd, ld, code, off_d, lab_d, k_d, S, rows, G, max_n, kmax, KT, work, gsize, nvalid, mg, vg, mr,
-         vr, pg, pr, zg, zr, status, st)
+         vr, pg, pr, zg, zr, status)
     R2, T = e((KT, G), i64), e((S, G), i64)
     # (the rank sums are part of the result for every method: they are what the tests pin exactly)
-    call("mcl_marker_rank_sums", xd, ld, code, lab_d, S, rows, G, max_n, kmax, KT, work, R2, T, st)
+    call("mcl_marker_rank_sums", xd, ld, code, lab_d, S, rows, G, max_n, kmax, KT, work, R2, T)
     sc, pv, nl, lfc, adj = (e((KT, G), f64) for _ in range(5))
     call("mcl_marker_test", METHODS[method], int(bool(tie_correct)), S, rows, G, kmax, KT, work, gsize, mg, vg, mr, vr, R2,
-         T, sc, pv, nl, lfc, st)
+         T, sc, pv, nl, lfc)
     names = e((KT, n_top), i64)
     o_sc, o_pv, o_adj, o_nl, o_lfc = (e((KT, n_top), f64) for _ in range(5))
     call("mcl_marker_rank_adjust", S, rows, G, kmax, KT, n_top, int(bool(rankby_abs)), work, sc, pv, nl, lfc, adj, names,
-         o_sc, o_pv, o_adj, o_nl, o_lfc, st)
+         o_sc, o_pv, o_adj, o_nl, o_lfc)
     bad = status.cpu().numpy()                                  # the one synchronisation
     if bad.any():
         s = int(np.flatnonzero(bad.any(axis=1))[0])

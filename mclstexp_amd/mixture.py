@@ -35,7 +35,7 @@ import torch
 
 from . import cluster
 from ._arrays import FLOAT_CODE, ArrayLike, Tensor, device, empty, matrix, stack_rows, upload
-from ._lib import call, current_stream
+from ._lib import call
 
 MAX_DIM = cluster.MAX_DIM          # D <= 64 and K <= 64 (csrc/mixture.hip)
 MAX_ROWS = cluster.MAX_ROWS
@@ -138,10 +138,10 @@ def gmm(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequence[i
     alls = [res[n] for n in ("labels_all", "weights_all", "means_all", "covariances_all", "precisions_cholesky_all",
                              "lower_bound_all", "score_all", "n_iter_all", "converged_all", "status_all")]
     call("mcl_gmm_fit", zd, zd.stride(0), off_d, S, rows, D, ks_d, k_max, R, code, init, float(tol), int(max_iter),
-         float(reg_covar), work, wb, *alls, current_stream())
+         float(reg_covar), work, wb, *alls)
     call("mcl_gmm_select", off_d, S, rows, D, ks_d, k_max, R, code, work, wb, *alls, res["labels"], res["resp"],
          res["weights"], res["means"], res["covariances"], res["precisions_cholesky"], res["lower_bound"], res["n_iter"],
-         res["converged"], res["status"], res["bic"], res["aic"], res["restart"], current_stream())
+         res["converged"], res["status"], res["bic"], res["aic"], res["restart"])
     res.update(init_labels=init, k=ks, offsets=off, covariance_type=covariance_type)
     if check:
         bad = np.flatnonzero((res["status_all"].cpu().numpy() != 0).any(axis=1))
@@ -180,7 +180,7 @@ def predict(z: ArrayLike, model: Dict[str, object], offsets: Optional[Sequence[i
            "score": e((S,), torch.float64)}
     res["log_resp"].fill_(float("-inf"))
     call("mcl_gmm_predict", zd, zd.stride(0), upload(off, dev), S, rows, D, upload(ks, dev), k_max, code, w, mu, pc,
-         res["log_prob_norm"], res["log_resp"], res["resp"], res["labels"], res["score"], current_stream())
+         res["log_prob_norm"], res["log_resp"], res["resp"], res["labels"], res["score"])
     return res
 
 
@@ -206,8 +206,7 @@ def m_step(z: ArrayLike, log_resp: ArrayLike, k: Union[int, Sequence[int]], offs
     wb = call("mcl_gmm_workspace_bytes", rows, S, 1, D, k_max)
     work = torch.empty((wb // 8,), device=dev, dtype=torch.float64)
     call("mcl_gmm_mstep", zd, zd.stride(0), upload(off, dev), S, rows, D, upload(ks, dev), k_max, code, lr, float(reg_covar),
-         work, wb, res["weights"], res["means"], res["covariances"], res["precisions_cholesky"], res["status"],
-         current_stream())
+         work, wb, res["weights"], res["means"], res["covariances"], res["precisions_cholesky"], res["status"])
     res.update(k=ks, offsets=off, covariance_type=covariance_type)
     return res
 
@@ -318,7 +317,7 @@ def validity(z: ArrayLike, labels: ArrayLike, offsets: Optional[Sequence[int]] =
     work = torch.empty((wb // 8,), device=dev, dtype=torch.float64)
     sil = torch.empty((rows,), device=dev, dtype=torch.float64)
     scores = torch.empty((S, 3), device=dev, dtype=torch.float64)
-    call("mcl_cluster_validity", zd, zd.stride(0), upload(off, dev), S, rows, D, t, work, wb, sil, scores, current_stream())
+    call("mcl_cluster_validity", zd, zd.stride(0), upload(off, dev), S, rows, D, t, work, wb, sil, scores)
     h = scores.cpu().numpy()
     return {"silhouette_samples": sil, "silhouette": h[:, 0].copy(), "calinski_harabasz": h[:, 1].copy(),
             "davies_bouldin": h[:, 2].copy()}

@@ -34,7 +34,8 @@ import torch
 
 from . import _arrays, cluster
 from . import preprocess as _pre       # expression_graph has an argument of the module's name
-from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, check_columns, cumulative_offsets, dense, device, empty, matrix,
+                      upload)
 from ._lib import call
 
 MAX_DIM = 64             # csrc/neighbors.hip
@@ -68,28 +69,8 @@ def validate_neighbors(n_neighbors: int) -> int:
 
 
 def _check_x(x: ArrayLike, offsets, n_neighbors: int) -> np.ndarray:
-    if not isinstance(x, Tensor) and np.asarray(x).ndim != 2:
-        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {np.asarray(x).shape}")
-    if len(x.shape) != 2:
-        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {tuple(x.shape)}")
-    rows, D = int(x.shape[0]), int(x.shape[1])
-    if D < 1 or D > MAX_DIM:
-        raise ValueError(f"x has {D} columns; the kernel handles 1 .. {MAX_DIM}")
+    rows, _ = check_columns(x, MAX_DIM)
     return validate_offsets(offsets, rows, n_neighbors)
-
-
-def _dense(a: ArrayLike, name: str, shape, dtype: torch.dtype, dev: torch.device) -> Tensor:
-    """``a`` as a dense device tensor of ``shape`` and ``dtype`` (host arrays are converted on the host)."""
-    t = a if isinstance(a, Tensor) else torch.as_tensor(np.asarray(a))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    if t.is_cuda and t.dtype != dtype:
-        raise ValueError(f"{name}: device tensors must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    if t.is_cuda and t.is_contiguous():
-        return t
-    out = torch.empty(tuple(shape), device=dev, dtype=dtype)
-    out.copy_(t if t.is_cuda else t.to(dtype))
-    return out
 
 
 # ----------------------------------------------------------------------------------------------------------- device
@@ -153,7 +134,7 @@ def smooth(knn_distances: ArrayLike, offsets: Optional[Sequence[int]] = None) ->
     off = validate_offsets(offsets, rows, k)
     dev = device("neighbors")
     plan = _Plan(off, k, dev)
-    dist = _dense(knn_distances, "knn_distances", (rows, k), torch.float64, dev)
+    dist = dense(knn_distances, "knn_distances", (rows, k), torch.float64, dev)
     e = empty(dev)
     rho, sigma = e((rows,), torch.float64), e((rows,), torch.float64)
     plan.smooth(dist, rho, sigma)
@@ -172,9 +153,9 @@ def connectivities(knn_indices: ArrayLike, knn_distances: ArrayLike, rho: ArrayL
             raise ValueError(f"{name}: expected shape {shape}, got {tuple(a.shape)}")
     dev = device("neighbors")
     plan = _Plan(off, k, dev)
-    idx = _dense(knn_indices, "knn_indices", (rows, k), torch.int32, dev)
-    dist = _dense(knn_distances, "knn_distances", (rows, k), torch.float64, dev)
-    r, s = _dense(rho, "rho", (rows,), torch.float64, dev), _dense(sigma, "sigma", (rows,), torch.float64, dev)
+    idx = dense(knn_indices, "knn_indices", (rows, k), torch.int32, dev)
+    dist = dense(knn_distances, "knn_distances", (rows, k), torch.float64, dev)
+    r, s = dense(rho, "rho", (rows,), torch.float64, dev), dense(sigma, "sigma", (rows,), torch.float64, dev)
     indptr, indices, data, nnz_off = plan.connectivities(idx, dist, r, s, mix)
     return {"indptr": indptr, "indices": indices, "data": data, "offsets": off, "nnz_offsets": nnz_off}
 

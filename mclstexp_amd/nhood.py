@@ -44,8 +44,8 @@ import numpy as np
 import torch
 
 from . import markers, spatial
-from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, upload, validate_offsets
-from ._lib import call, current_stream
+from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, nanmean, upload, validate_offsets
+from ._lib import call
 from .ligrec import kept_sizes
 
 MAX_ROWS = 16384         # csrc/nhood.hip: the uint16 permutation tables and neighbour lists
@@ -167,7 +167,7 @@ def _prepare(labels, rows: int, off: np.ndarray, kk: np.ndarray, dev: torch.devi
     i32 = torch.int32
     off_d, k_d = upload(off, dev), upload(kk, dev)
     order, start, koff, status = e((rows,), i32), e((S, kmax + 1), i32), e((S + 1,), torch.int64), e((S, 4), i32)
-    call("mcl_ligrec_prepare", off_d, lab_d, k_d, S, rows, max_n, kmax, order, start, koff, status, current_stream())
+    call("mcl_ligrec_prepare", off_d, lab_d, k_d, S, rows, max_n, kmax, order, start, koff, status)
     return {"offsets_device": off_d, "k_device": k_d, "order": order, "start": start, "kept_offsets": koff, "status": status,
             "S": S, "max_n": max_n, "kmax": kmax}
 
@@ -209,7 +209,6 @@ def nhood_device(labels, graph: Dict[str, object], k=None, n_perms: int = 1000, 
     w_d = w.to(dev).contiguous() if isinstance(w, Tensor) else upload(np.asarray(w, dtype=np.float64), dev)
     prep = _prepare(labels, rows, off, kk, dev)
     e = empty(dev)
-    st = current_stream()
     max_n = prep["max_n"]
     work = e((int(call("mcl_nhood_workspace_bytes", rows, kw)) // 8 + 1,), torch.float64)
     count = e((S, kmax, kmax), torch.int32)
@@ -220,13 +219,13 @@ def nhood_device(labels, graph: Dict[str, object], k=None, n_perms: int = 1000, 
         table_work = e((int(call("mcl_spatial_workspace_bytes", rows, 0, P)) // 8 + 1,), torch.float64)
         table = table_work.view(torch.int16)[:P * rows]
         if host_table is None:
-            call("mcl_spatial_permutations", prep["kept_offsets"], S, rows, max_n, P, seed, table_work, st)
+            call("mcl_spatial_permutations", prep["kept_offsets"], S, rows, max_n, P, seed, table_work)
         elif host_table.size:
             table[:host_table.size].copy_(torch.from_numpy(host_table))
         stats = e((S, 4, kmax, kmax), torch.int64)
         out.update({"stats": stats, "table": table, "workspace": table_work})
     call("mcl_nhood_counts", prep["offsets_device"], prep["kept_offsets"], prep["order"], prep["start"], prep["k_device"], S,
-         rows, max_n, kmax, nbr_d, w_d, kw, table_work, P, work, count, stats, prep["status"], st)
+         rows, max_n, kmax, nbr_d, w_d, kw, table_work, P, work, count, stats, prep["status"])
     _raise_status(prep["status"])
     return out
 
@@ -342,13 +341,12 @@ def co_occurrence(coords: ArrayLike, labels, offsets: Optional[Sequence[int]] = 
     c_d = upload(host_c, dev) if host_c is not None else _coords(dev_c, dev)[1]
     prep = _prepare(labels, rows, off, kk, dev)
     e = empty(dev)
-    st = current_stream()
     work = e((int(call("mcl_cooccur_workspace_bytes", rows)) // 8 + 1,), torch.float64)
     r2_d = upload(rad * rad, dev)                               # r_t r_t, rounded once
     pairs, occ = e((S, T, kmax, kmax), torch.int32), e((S, T, kmax, kmax), torch.float64)
     call("mcl_cooccur_counts", c_d, prep["offsets_device"], prep["order"], prep["start"], prep["k_device"], S, rows,
-         prep["max_n"], kmax, r2_d, T, work, pairs, prep["status"], st)
-    call("mcl_cooccur_scores", prep["k_device"], S, kmax, T, pairs, occ, st)
+         prep["max_n"], kmax, r2_d, T, work, pairs, prep["status"])
+    call("mcl_cooccur_scores", prep["k_device"], S, kmax, T, pairs, occ)
     _raise_status(prep["status"])
     d = {"pairs": pairs, "occ": occ, "start": prep["start"], "offsets": off, "k": kk}
     return [{"pairs": host["pairs"][s, :, :K, :K].astype(np.int64), "occ": host["occ"][s, :, :K, :K].copy(),
@@ -419,11 +417,6 @@ def recovery_scores(rp: Dict[str, object], rt: Dict[str, object], match: np.ndar
     return {"pearson_z": spatial.pearson(zp, zt), "sign_agreement": sign, "pearson_occ": occ, "n_cells": int(ok.sum())}
 
 
-def _nanmean(v) -> float:
-    v = np.asarray(v, dtype=np.float64)
-    return float(v[np.isfinite(v)].mean()) if np.isfinite(v).any() else float("nan")
-
-
 def arrangement_recovery(pred_labels: Sequence[Sequence], true_labels: Sequence[Sequence], coords: Sequence[ArrayLike],
                          **kw) -> Dict[str, object]:
     """Are the predicted domains arranged in the tissue the way the measured ones are?  Both label sets are analysed on
@@ -456,7 +449,7 @@ def arrangement_recovery(pred_labels: Sequence[Sequence], true_labels: Sequence[
         for key, v in recovery_scores(a, b, match).items():
             cols[key].append(v)
     out = {key: np.asarray(v) for key, v in cols.items()}
-    out.update({f"mean_{key}": _nanmean(out[key]) for key in ("pearson_z", "sign_agreement", "pearson_occ")})
+    out.update({f"mean_{key}": nanmean(out[key]) for key in ("pearson_z", "sign_agreement", "pearson_occ")})
     out.update({"matching": matching, "pred": rp, "true": rt})
     return out
 

@@ -39,9 +39,9 @@ import numpy as np
 import torch
 
 from . import neighbors
-from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, stack_rows,
-                      upload, validate_offsets)
-from ._lib import call, current_stream
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, dense, device, empty, load_gene_major, matrix,
+                      stack_rows, upload, validate_offsets)
+from ._lib import call
 
 MAX_ROWS = 16384         # csrc/spatial.hip: 14 index bits in a permutation key, uint16 tables
 MAX_K = 64
@@ -127,20 +127,6 @@ def check_permutations(permutations, sizes: np.ndarray) -> np.ndarray:
     return np.concatenate(parts)
 
 
-def _dense(a: ArrayLike, name: str, shape, dtype: torch.dtype, dev: torch.device, integer: bool) -> Tensor:
-    t = a if isinstance(a, Tensor) else torch.as_tensor(np.asarray(a))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    if t.is_cuda:
-        if t.dtype != dtype:
-            raise ValueError(f"{name}: device tensors must be {str(dtype).replace('torch.', '')}, got {t.dtype}")
-    elif integer != (not t.dtype.is_floating_point and t.dtype != torch.bool):
-        raise ValueError(f"{name}: expected {'integers' if integer else 'floating-point values'}, got {t.dtype}")
-    out = torch.empty(tuple(shape), device=dev, dtype=dtype)      # always a copy: the kernel's outputs alias nothing
-    out.copy_(t if t.is_cuda else t.to(dtype))
-    return out
-
-
 # ----------------------------------------------------------------------------------------------------------- device
 def lattice(coords: Optional[ArrayLike] = None, offsets: Optional[Sequence[int]] = None, k: int = 8, prune: str = "NA",
             row_standardise: bool = True, nbr: Optional[ArrayLike] = None, w: Optional[ArrayLike] = None) -> Dict[str, object]:
@@ -174,8 +160,8 @@ def lattice(coords: Optional[ArrayLike] = None, offsets: Optional[Sequence[int]]
     e = empty(dev)
     S, max_n = int(off.size - 1), int(np.diff(off).max())
     if given:
-        nbr_d = _dense(nbr, "nbr", (rows, k), torch.int32, dev, True)
-        w_d = _dense(w, "w", (rows, k), torch.float64, dev, False)
+        nbr_d = dense(nbr, "nbr", (rows, k), torch.int32, dev, copy=True, integer=True)      # copies: the kernel's outputs
+        w_d = dense(w, "w", (rows, k), torch.float64, dev, copy=True, integer=False)         # alias nothing
         idx = dist = None
     else:
         idx, dist = neighbors.knn(coords, off, k + 1)
@@ -184,7 +170,7 @@ def lattice(coords: Optional[ArrayLike] = None, offsets: Optional[Sequence[int]]
     work = e((int(call("mcl_spatial_workspace_bytes", rows, k + 1, 0)) // 8 + 1,), torch.float64)
     off_d = upload(off, dev)
     call("mcl_spatial_lattice", idx, dist, off_d, S, rows, max_n, k, code, int(bool(row_standardise)), int(given), work,
-         nbr_d, w_d, deg, consts, status, current_stream())
+         nbr_d, w_d, deg, consts, status)
     bad = status.cpu().numpy()                                  # the one synchronisation
     for col, what in enumerate(_STATUS):
         if bad[:, col].any():
@@ -224,30 +210,29 @@ def autocorr_device(x: ArrayLike, graph: Dict[str, object], n_perms: int = 0, se
         mask |= 1 << int(call("mcl_spatial_columns", int(n)))
     code, ld = FLOAT_CODE[xd.dtype], int(xd.stride(0))
     off_d = graph["offsets_device"]
-    st = current_stream()
     status = torch.zeros((S,), device=dev, dtype=i32)
     mean, den, stat = e((S, G), f64), e((S, G), f64), e((2, S, G), f64)
     call("mcl_spatial_stats", xd, ld, code, off_d, S, rows, G, max_n, k, mask, graph["nbr"], graph["w"], graph["consts"],
-         None, 1, mean, den, stat, status, st)
+         None, 1, mean, den, stat, status)
     zn, pv, nl, adj = (e((2, S, G), f64) for _ in range(4))
     prank, scratch = e((2, S, G), i32), e((2, S, G), f64)
     call("mcl_spatial_moments", off_d, S, rows, G, max_n, graph["consts"], stat, int(bool(two_tailed)), prank, scratch, zn,
-         pv, nl, adj, st)
+         pv, nl, adj)
     out = {"stat": stat, "mean": mean, "den": den, "z_norm": zn, "pval_norm": pv, "neglog10_pval_norm": nl,
            "pval_norm_adj": adj, "n_perms": P}
     if P:
         work = e((int(call("mcl_spatial_workspace_bytes", rows, 0, P)) // 8 + 1,), f64)
         table = work.view(torch.int16)[:P * rows]
         if host_table is None:
-            call("mcl_spatial_permutations", off_d, S, rows, max_n, P, seed, work, st)
+            call("mcl_spatial_permutations", off_d, S, rows, max_n, P, seed, work)
         else:
             table.copy_(torch.from_numpy(host_table))
         sims = e((2, S, P, G), f64)
         call("mcl_spatial_stats", xd, ld, code, off_d, S, rows, G, max_n, k, mask, graph["nbr"], graph["w"],
-             graph["consts"], work, P, None, None, sims, status, st)
+             graph["consts"], work, P, None, None, sims, status)
         count = e((2, S, G), i32)
         ps, pz, ms, vs = (e((2, S, G), f64) for _ in range(4))
-        call("mcl_spatial_perm_summary", S, G, P, stat, sims, int(bool(two_tailed)), count, ps, pz, ms, vs, st)
+        call("mcl_spatial_perm_summary", S, G, P, stat, sims, int(bool(two_tailed)), count, ps, pz, ms, vs)
         out.update({"sims": sims, "count_sim": count, "pval_sim": ps, "pval_z_sim": pz, "mean_sim": ms, "var_sim": vs,
                     "table": table, "workspace": work})
     bad = status.cpu().numpy()                                  # the one synchronisation

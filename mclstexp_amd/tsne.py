@@ -36,7 +36,8 @@ import numpy as np
 import torch
 
 from . import _arrays, cluster
-from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, stack_rows, upload
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, check_columns, cumulative_offsets, dense, device, empty, matrix,
+                      stack_rows, upload)
 from ._lib import call
 
 MAX_DIM = 64             # csrc/tsne.hip
@@ -186,33 +187,13 @@ class _Plan:
 
 
 def _check_x(x: ArrayLike, offsets, perplexity: float):
-    if not isinstance(x, Tensor) and np.asarray(x).ndim != 2:
-        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {np.asarray(x).shape}")
-    if len(x.shape) != 2:
-        raise ValueError(f"x: expected a 2-D (rows, D) array, got shape {tuple(x.shape)}")
-    rows, D = int(x.shape[0]), int(x.shape[1])
-    if D < 1 or D > MAX_DIM:
-        raise ValueError(f"x has {D} columns; the kernel handles 1 .. {MAX_DIM}")
+    rows, D = check_columns(x, MAX_DIM)
     off = validate_offsets(offsets, rows)
     seg = np.diff(off)
     if not perplexity > 0 or perplexity >= seg.min():
         raise ValueError(f"perplexity must be positive and less than the rows of every segment; got {perplexity}, "
                          f"segment sizes {seg.tolist()}")
     return off, seg, D
-
-
-def _dense_f64(a: ArrayLike, name: str, shape, dev: torch.device, copy: bool = False) -> Tensor:
-    """``a`` as a dense fp64 device tensor of ``shape`` (``copy``: never the caller's own storage)."""
-    t = a if isinstance(a, Tensor) else torch.as_tensor(np.asarray(a))
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
-    if t.is_cuda and t.dtype != torch.float64:
-        raise ValueError(f"{name}: device tensors must be float64, got {t.dtype}")
-    if t.is_cuda and t.is_contiguous() and not copy:
-        return t
-    out = torch.empty(tuple(shape), device=dev, dtype=torch.float64)
-    out.copy_(t if t.is_cuda else t.to(torch.float64))
-    return out
 
 
 def _segment_table(v: Union[float, Sequence[float]], S: int, name: str) -> np.ndarray:
@@ -254,8 +235,8 @@ def gradient(P: ArrayLike, Y: ArrayLike, offsets: Optional[Sequence[int]] = None
     ex = _segment_table(exaggeration, seg.size, "exaggeration")
     dev = device("tsne")
     plan = _Plan(off, dev)
-    Pd = _dense_f64(P, "P", tuple(P.shape), dev)
-    Yd = _dense_f64(Y, "Y", (rows, 2), dev)
+    Pd = dense(P, "P", tuple(P.shape), torch.float64, dev)
+    Yd = dense(Y, "Y", (rows, 2), torch.float64, dev)
     params = np.stack([ex, np.zeros_like(ex), np.zeros_like(ex), np.ones_like(ex), np.zeros_like(ex)], axis=1)
     e = empty(dev)
     grad, kl_d = e((rows, 2), torch.float64), e((plan.S,), torch.float64)
@@ -273,8 +254,9 @@ def update(Y: ArrayLike, grad: ArrayLike, upd: ArrayLike, gains: ArrayLike, offs
     m, lr = _segment_table(momentum, S, "momentum"), _segment_table(learning_rate, S, "learning_rate")
     dev = device("tsne")
     plan = _Plan(off, dev)
-    Yd, ud, gd = (_dense_f64(a, n, (rows, 2), dev, copy=True) for a, n in ((Y, "Y"), (upd, "update"), (gains, "gains")))
-    g = _dense_f64(grad, "grad", (rows, 2), dev)
+    Yd, ud, gd = (dense(a, n, (rows, 2), torch.float64, dev, copy=True)
+                  for a, n in ((Y, "Y"), (upd, "update"), (gains, "gains")))
+    g = dense(grad, "grad", (rows, 2), torch.float64, dev)
     params = np.stack([np.ones(S), m, lr, np.ones(S), np.zeros(S)], axis=1)
     norm2 = empty(dev)((S,), torch.float64)
     plan.update(g, upload(params, dev), Yd, ud, gd, norm2)
@@ -317,7 +299,7 @@ def tsne(x: ArrayLike, offsets: Optional[Sequence[int]] = None, perplexity: floa
     aff = joint_probabilities(x, off, perplexity, float32_distances)
     plan, P = aff["_plan"], aff["P"]
     e = empty(dev)
-    Y = _dense_f64(y0, "init", (rows, 2), dev, copy=True)
+    Y = dense(y0, "init", (rows, 2), torch.float64, dev, copy=True)
     grad, upd, gains = (e((rows, 2), torch.float64) for _ in range(3))
     stats = e((2, S), torch.float64)                  # kl, squared gradient norm: the one read per check
     sched = Schedule(seg, n_iter, early_exaggeration, lr)

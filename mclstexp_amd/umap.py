@@ -37,9 +37,8 @@ import numpy as np
 import torch
 
 from . import _arrays, neighbors
-from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, matrix, upload
+from ._arrays import FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, dense, device, empty, matrix, upload
 from ._lib import call
-from .neighbors import _dense
 
 MAX_ROWS = 16384         # csrc/umap.hip
 MAX_SEGMENTS = 65535
@@ -192,9 +191,9 @@ def layout(graph: Dict[str, object], init: Union[str, ArrayLike] = "pca", x: Opt
         a, b = find_ab_params(spread, min_dist)
     dev = device("umap")
     e = empty(dev)
-    indptr = _dense(graph["indptr"], "indptr", (rows + S,), torch.int64, dev)
-    indices = _dense(graph["indices"], "indices", (total,), torch.int32, dev) if total else e((1,), torch.int32)
-    data = _dense(graph["data"], "data", (total,), torch.float64, dev) if total else e((1,), torch.float64)
+    indptr = dense(graph["indptr"], "indptr", (rows + S,), torch.int64, dev)
+    indices = dense(graph["indices"], "indices", (total,), torch.int32, dev) if total else e((1,), torch.int32)
+    data = dense(graph["data"], "data", (total,), torch.float64, dev) if total else e((1,), torch.float64)
     off_d, nnz_off_d, epochs_d = upload(off, dev), upload(nnz_off, dev), upload(epochs, dev)
     work = e((max(int(call("mcl_umap_workspace_bytes", total, S)), 8) // 8 + 1,), torch.float64)
     counters = e((S, 2), torch.int64)
@@ -207,7 +206,7 @@ def layout(graph: Dict[str, object], init: Union[str, ArrayLike] = "pca", x: Opt
              FLOAT_CODE[xd.dtype] if xd is not None else 1,
              int(xd.shape[1]) if xd is not None else 0, off_d, *sizes, seed64, Y[0])
     else:
-        Y[0].copy_(_dense(init, "init", (rows, 2), torch.float64, dev))
+        Y[0].copy_(dense(init, "init", (rows, 2), torch.float64, dev))
     call("mcl_umap_prepare", data, nnz_off_d, epochs_d, S, total, int(np.diff(nnz_off).max()), max_epochs, rate, work, counters)
     count = max_epochs if stop_after is None else min(int(stop_after), max_epochs)
     call("mcl_umap_epochs", 0, count, indptr, indices, off_d, nnz_off_d, epochs_d, *sizes, total, max_epochs,

@@ -82,6 +82,33 @@ def test_matrix_host_conversions():
         A.matrix(np.ones(3), "x", CPU, A.FLOAT_CODE, torch.float64, RuntimeError)
 
 
+def test_dense_checks_shape_then_kind_and_converts_host_arrays():
+    d = A.dense(np.arange(6).reshape(2, 3), "nbr", (2, 3), torch.int32, CPU, integer=True)
+    assert d.dtype == torch.int32 and d.is_contiguous() and d.tolist() == [[0, 1, 2], [3, 4, 5]]
+    assert A.dense([[1, 2]], "w", (1, 2), torch.float64, CPU).dtype == torch.float64         # integer=None: any host kind
+    src = torch.ones((2, 2), dtype=torch.float64)
+    assert A.dense(src, "Y", (2, 2), torch.float64, CPU, copy=True).data_ptr() != src.data_ptr()
+    with pytest.raises(ValueError, match=r"nbr: expected shape \(2, 3\), got \(3, 2\)"):    # the shape comes first
+        A.dense(np.ones((3, 2)), "nbr", (2, 3), torch.int32, CPU, integer=True)
+    with pytest.raises(ValueError, match=r"nbr: expected integers, got torch.float64"):
+        A.dense(np.ones((2, 3)), "nbr", (2, 3), torch.int32, CPU, integer=True)
+    with pytest.raises(ValueError, match=r"nbr: expected integers, got torch.bool"):
+        A.dense(np.ones((2, 3), bool), "nbr", (2, 3), torch.int32, CPU, integer=True)
+    with pytest.raises(ValueError, match=r"w: expected floating-point values, got torch.int64"):
+        A.dense(np.ones((2, 3), np.int64), "w", (2, 3), torch.float64, CPU, integer=False)
+
+
+def test_check_columns_and_nanmean():
+    assert A.check_columns(np.ones((5, 64)), 64) == (5, 64) and A.check_columns(torch.ones(3, 1), 64) == (3, 1)
+    for bad in (np.ones(4), np.ones((2, 2, 2)), torch.ones(4)):
+        with pytest.raises(ValueError, match=r"x: expected a 2-D \(rows, D\) array, got shape"):
+            A.check_columns(bad, 64)
+    for cols in (0, 65):
+        with pytest.raises(ValueError, match=rf"x has {cols} columns; the kernel handles 1 \.\. 64"):
+            A.check_columns(np.ones((3, cols)), 64)
+    assert A.nanmean([1.0, np.nan, 3.0, np.inf]) == 2.0 and np.isnan(A.nanmean([np.nan])) and np.isnan(A.nanmean([]))
+
+
 def test_count_slides_follow_the_same_helper():
     from mclstexp_amd import preprocess
     assert preprocess._slide(np.ones((2, 3), np.int64), "s", CPU).dtype == torch.int32

@@ -172,10 +172,10 @@ def test_header_and_prototypes_agree_for_the_new_names():
     want, have = header_prototypes(), table_prototypes(_lib.PROTOTYPES, _lib._RESTYPES)
     for name in NAMES:
         assert want[name] == have[name], name
-        assert "stream" not in want[name][1]                  # the stream is a trailing void*: see the header
-        assert want[name][1][-1] == "ptr" or name == NAMES[0]
+        assert "stream" not in want[name][1][:-1]
+        assert want[name][1][-1] == "stream" or name == NAMES[0]      # the five launching names take the stream last
     assert want[NAMES[0]] == ("i64", ["i64", "i64", "i32", "i32"])
-    assert _lib._SIGNATURES["mcl_leiden_init"][2] is False    # call() appends nothing: leiden.py passes current_stream()
+    assert _lib._SIGNATURES["mcl_leiden_init"][2] is True     # call() appends torch's current stream
 
 
 def test_abi_and_argument_errors_without_gpu():

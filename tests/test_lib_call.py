@@ -1,5 +1,6 @@
 """``_lib.call``: the one checked path from Python into the C ABI.  CPU tests (argument checks happen before the library is
-touched), a source test (no module reaches the library another way) and one GPU test (same launch as raw ctypes)."""
+touched), a source test (no module reaches the library another way) and two GPU tests (same launch as raw ctypes; a stage
+module's launch follows torch's current stream)."""
 import ctypes as C
 import glob
 import os
@@ -61,6 +62,10 @@ def test_wrong_argument_count_names_the_entry_point_and_both_counts(untouched):
         call("mcl_add_f32", None, None, None)
     with pytest.raises(TypeError, match=r"mcl_add_f32 takes 4 arguments \(the stream is appended\), 5 given"):
         call("mcl_add_f32", None, None, None, 8, None)                      # (passing the stream by hand is one too many)
+    with pytest.raises(TypeError, match=r"mcl_edge_agreement takes 8 arguments \(the stream is appended\), 9 given"):
+        call("mcl_edge_agreement", None, 1, 4, None, None, None, 2, None, None)     # (so it is for a stage's entry point)
+    with pytest.raises(RuntimeError, match=r"mcl_edge_agreement: argument 3 is on cpu"):      # eight pass the count
+        call("mcl_edge_agreement", None, 1, 4, torch.zeros(4, dtype=torch.int32), None, None, 2, None)
     with pytest.raises(TypeError, match=r"mcl_bn_workspace_floats takes 3 arguments, 2 given"):
         call("mcl_bn_workspace_floats", 4, 8)
     with pytest.raises(RuntimeError, match="no entry point mcl_nope"):
@@ -75,7 +80,10 @@ def test_signatures_follow_the_table():
         assert returns_value == (name in _lib._RESTYPES)
         assert len(pointer) == nargs
         assert pointer == tuple(t is C.c_void_p for t in argtypes[:nargs]), name
-    assert sum(s[2] for s in _lib._SIGNATURES.values()) == 151
+    # every status-returning entry point enqueues work and is handed the stream; no value-returning one is
+    streamed = {name for name, s in _lib._SIGNATURES.items() if s[2]}
+    assert streamed == set(_lib.PROTOTYPES) - set(_lib._RESTYPES)
+    assert len(streamed) >= 182 and len(_lib._RESTYPES) >= 44          # (floors: neither set is quietly empty)
 
 
 @pytest.fixture
@@ -162,3 +170,22 @@ def test_call_launches_exactly_what_raw_ctypes_launches():
         call("mcl_add_f32", a, b.cpu(), via, n)
     torch.cuda.synchronize()
     assert raw.view(torch.int32).equal(via.view(torch.int32))
+
+
+@pytest.mark.gpu
+def test_a_stage_entry_point_follows_the_current_stream():
+    """``hmrf.edge_agreement`` passes no stream: ``call`` hands ``mcl_edge_agreement`` torch's current one.  One slide of 4
+    spots on a ring, 2 neighbour slots of weight 1, labels 0 0 1 1: every spot agrees with one of its two neighbours."""
+    import numpy as np
+    from mclstexp_amd import hmrf
+    graph = {"nbr": np.array([[3, 1], [0, 2], [1, 3], [2, 0]], dtype=np.int32), "w": np.ones((4, 2)), "offsets": [0, 4]}
+    labels = np.array([0, 0, 1, 1], dtype=np.int32)
+    default = hmrf.edge_agreement(labels, graph)
+    assert default.shape == (1,) and default[0] == 0.5
+    side = torch.cuda.Stream()
+    with torch.cuda.stream(side), _lib.AbiTimer(["mcl_edge_agreement"]) as t:
+        on_side = hmrf.edge_agreement(labels, graph)
+    (_, _, args), = t.records["mcl_edge_agreement"]
+    assert len(args) == 9 and args[-1] == side.cuda_stream != torch.cuda.current_stream().cuda_stream
+    assert on_side.tobytes() == default.tobytes()
+    torch.cuda.synchronize()

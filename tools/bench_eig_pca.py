@@ -89,7 +89,7 @@ def run(names, calls):
                 ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
                 ev[0].record()
                 _lib.call("mcl_sym_eig_top", gram, goff_d, m_d, S, max_m, sum_m, n_comps, st, values, vectors, eoff_d, cert,
-                          work, _lib.current_stream())
+                          work)
                 ev[1].record()
                 torch.cuda.synchronize()
                 stages[st].append(ev[0].elapsed_time(ev[1]))

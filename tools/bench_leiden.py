@@ -63,8 +63,7 @@ def run(calls, with_networkx):
         n_cur, long_rows = r._sizes(st, 0)
         with _lib.AbiTimer(["mcl_leiden_move_sweeps"]) as t:
             for _ in range(4):
-                _lib.call("mcl_leiden_move_sweeps", 1, 0, n_cur, long_rows, r.max_sweeps, *r.graph_args, r.gamma, r.work,
-                          _lib.current_stream())
+                _lib.call("mcl_leiden_move_sweeps", 1, 0, n_cur, long_rows, r.max_sweeps, *r.graph_args, r.gamma, r.work)
         ms = t.summary()["mcl_leiden_move_sweeps"]["ms"]
         need = sweep_bytes(rows, nnz)
         entry = {"segments": int(seg.size), "rows": rows, "k": k, "nnz": nnz, "leiden_wall_ms_median": walls[len(walls) // 2],
