@@ -31,6 +31,19 @@ def empty(dev: torch.device) -> Callable[..., Tensor]:
 
 
 # ------------------------------------------------------------------------------------------------------ host checks
+def check_int(v, name: str, lo: int, hi: Optional[int] = None) -> int:
+    """``v`` as an int when it is an integer (no bool) in ``lo .. hi``, or ``>= lo`` where there is no ``hi``."""
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError(f"{name} must be an integer {f'>= {lo}' if hi is None else f'in {lo} .. {hi}'}, got {v!r}")
+    return int(v)
+
+
+def check_flag(v, name: str) -> bool:
+    if not isinstance(v, (bool, np.bool_)):
+        raise ValueError(f"{name} must be a bool, got {v!r}")
+    return bool(v)
+
+
 def cumulative_offsets(sizes) -> np.ndarray:
     """[0, sizes[0], sizes[0] + sizes[1], ...] as int64."""
     return np.concatenate([[0], np.cumsum(np.asarray(sizes, dtype=np.int64))]).astype(np.int64)

@@ -136,7 +136,8 @@ def pca_scores_slides(xs: Sequence[ArrayLike], n_comps: int = N_COMPS, solver: s
 
 
 # -------------------------------------------------------------------------------------------------------- k-means
-def _k_per_segment(k: Union[int, Sequence[int]], seg: np.ndarray) -> np.ndarray:
+def k_per_segment(k: Union[int, Sequence[int]], seg: np.ndarray) -> np.ndarray:
+    """``k`` as int32 per segment: an int stands for every segment; each 1 .. MAX_DIM and at most the segment's rows."""
     ks = np.asarray(k)
     if not np.issubdtype(ks.dtype, np.integer):
         raise ValueError(f"k must be an int or one int per segment, got {k!r}")
@@ -191,7 +192,7 @@ def kmeans(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequenc
         raise ValueError(f"z has {D} columns; the kernel handles 1 .. {MAX_DIM}")
     off = validate_offsets(offsets, rows)
     seg = np.diff(off)
-    ks = _k_per_segment(k, seg)
+    ks = k_per_segment(k, seg)
     S, k_max = ks.size, int(ks.max())
     if not (tol >= 0.0) or int(max_iter) < 1:
         raise ValueError(f"tol must be >= 0 and max_iter >= 1, got {tol}, {max_iter}")
@@ -309,7 +310,7 @@ def cluster_slides(preds: Sequence[ArrayLike], labels: Sequence[Sequence], undet
         raise ValueError(f"at most {MAX_DIM} distinct labels per slide, got {ks.tolist()}")
     dev = device("cluster")
     x, off = stack_rows([_take_rows(p, e[0], dev) for p, e in zip(preds, enc)], "preds", dev)
-    _k_per_segment(ks, np.diff(off))
+    k_per_segment(ks, np.diff(off))
     z = pca_scores(x, off, n_comps, solver)
     km = kmeans(z, ks, off, seed_rows=seed_rows, n_init=n_init, seed=seed, tol=tol, max_iter=max_iter,
                 segment_base=segment_base)

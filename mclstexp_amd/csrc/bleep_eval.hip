@@ -142,17 +142,6 @@ __global__ __launch_bounds__(KC_THREADS) void knn_combine_kernel(
 }
 
 // ----------------------------------------------------------------------------------------------------- mcl_cell_pearson
-__device__ __forceinline__ double wave_min_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ double wave_max_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 template <typename TP, typename TT>
 __global__ __launch_bounds__(256) void cell_pearson_kernel(const TP* __restrict__ pred, long long ldp,
                                                            const TT* __restrict__ tru, long long ldt, long long rows, int G,
@@ -173,8 +162,8 @@ __global__ __launch_bounds__(256) void cell_pearson_kernel(const TP* __restrict_
   }
   sp = wave_sum(sp);
   st = wave_sum(st);
-  pmin = wave_min_f64(pmin); pmax = wave_max_f64(pmax);
-  tmin = wave_min_f64(tmin); tmax = wave_max_f64(tmax);
+  pmin = wave_min(pmin); pmax = wave_max(pmax);
+  tmin = wave_min(tmin); tmax = wave_max(tmax);
   const double pm = sp / (double)G, tm = st / (double)G;
   double sxy = 0.0, sxx = 0.0, syy = 0.0;
   for (int g = lane; g < G; g += 64) {

@@ -206,17 +206,11 @@ __global__ __launch_bounds__(256) void pca_scores_kernel(const T* __restrict__ x
 }
 
 // ----------------------------------------------------------------------------------------------------------- k-means
-// the counter-based generator of csrc/step_misc.hip's dropout (splitmix64 finaliser), keyed by (seed, segment, restart, draw)
-__device__ __forceinline__ unsigned long long km_mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
+// the counter-based generator of csrc/step_misc.hip's dropout (mix64), keyed by (seed, segment, restart, draw)
 __device__ __forceinline__ double km_uniform(unsigned long long seed, int seg, int r, int draw) {
-  unsigned long long h = km_mix64(seed ^ km_mix64((unsigned long long)(unsigned)seg));
-  h = km_mix64(h ^ (unsigned long long)(unsigned)r);
-  h = km_mix64(h ^ (unsigned long long)(unsigned)draw);
+  unsigned long long h = mix64(seed ^ mix64((unsigned long long)(unsigned)seg));
+  h = mix64(h ^ (unsigned long long)(unsigned)r);
+  h = mix64(h ^ (unsigned long long)(unsigned)draw);
   return (double)(h >> 32) * (1.0 / 4294967296.0);   // 32 random bits: u * total < total also after rounding
 }
 

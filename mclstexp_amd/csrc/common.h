@@ -56,22 +56,8 @@ static inline int mcl_cu_count() {
   }
   return cached[d];
 }
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+// blocks of b that cover a
+static inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // csrc/tsne.hip, csrc/neighbors.hip: d_ij = sum_k (x_ik - x_jk)^2 in index order, products and sums rounded separately (no
 // contraction: the value is the one numpy's elementwise arithmetic gives, so two kernels -- and the float32 rounding of

@@ -1,8 +1,9 @@
 // Device types and helpers shared by the gfx950 kernels (included from common.h).  A helper that rounds or loads
 // differently from the ones here keeps a name of its own in its file (gemm.hip f2bf_rne_finite: no inf / NaN handling;
-// dense_block.hip bn_relu_chunk_f4; the buffer descriptors c0_rsrc / raw_rsrc).
+// dense_block.hip bn_relu_chunk_f4; the buffer descriptors c0_rsrc / raw_rsrc; spatial.hip sp_slide_rows).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <float.h>
 
 typedef unsigned short bf16_t;                                   // bf16 bits
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -90,11 +91,121 @@ __device__ __forceinline__ float half_wave_sum(float x) {
   return x;
 }
 
+// 64-lane butterfly reductions: every lane returns the wave's sum / maximum / minimum
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ long long wave_sum(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_max(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// the sum over a 256-thread workgroup in a fixed order: the butterfly inside each wave, then waves 0 + 1 + 2 + 3.  Every
+// thread returns the same value.  ``red`` holds 4 doubles.  LEAD: a barrier ahead of the store, so that ``red`` may still be
+// being read from the reduction before; without it callers alternate two slots.
+template <bool LEAD>
+__device__ __forceinline__ double block_sum4(double v, double* red) {
+  v = wave_sum(v);
+  if (LEAD) __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
 // the lane id, made opaque to the compiler: everything derived from it is recomputed where it is used instead of being
 // hoisted out of the loop into live registers
 __device__ __forceinline__ int opaque_lane(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
+}
+
+// ---- order-preserving bit patterns: a < b <=> order_key(a) < order_key(b), -0.0 just below +0.0; a NaN with the sign bit
+// clear sorts above +inf (as torch.topk treats it).  key_value is the inverse.
+__device__ __forceinline__ unsigned order_key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ float key_value(unsigned k) {
+  const unsigned u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
+  return __uint_as_float(u);
+}
+__device__ __forceinline__ u64 order_key(double v) {
+  const u64 b = (u64)__double_as_longlong(v);
+  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double key_value(u64 k) {
+  const u64 b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
+  return __longlong_as_double((long long)b);
+}
+
+// ---- segments: the rows (spots of a slide) and stored entries a workgroup owns, read from device-resident offsets
+// rows of segment s, first row in *r0_out (always written); 0 where the offsets break what the launch was sized by
+// (min_n .. max_n rows each, ``rows`` in all): nothing is read or written then
+__device__ __forceinline__ int segment_rows(const long long* __restrict__ offsets, int s, long long rows, int min_n,
+                                            int max_n, long long* r0_out) {
+  const long long r0 = offsets[s], r1 = offsets[s + 1];
+  *r0_out = r0;
+  if (r0 < 0 || r1 - r0 < min_n || r1 > rows || r1 - r0 > max_n) return 0;
+  return (int)(r1 - r0);
+}
+// the same check for the kernels that test it as a condition: first row and rows of segment s, written only where it
+// holds (segment_rows in their place changes their code).  A segment has 2 rows at the least, whatever min_n says: the two
+// terms stand apart because max(2, min_n) changes the code of neighbors.hip, whose min_n is the k of the launch
+__device__ __forceinline__ bool segment_span(const long long* off, int s, int min_n, int max_n, long long rows, long long* o,
+                                             int* n) {
+  const long long lo = off[s], len = off[s + 1] - lo;
+  if (lo < 0 || len < 2 || len < min_n || len > max_n || lo + len > rows) return false;
+  *o = lo;
+  *n = (int)len;
+  return true;
+}
+// the stored entries of segment s: false where nnz_off does not fit nnz_total
+__device__ __forceinline__ bool segment_entries(const long long* nnz_off, int s, long long nnz_total, long long* base,
+                                                long long* count) {
+  const long long lo = nnz_off[s], len = nnz_off[s + 1] - lo;
+  if (lo < 0 || len < 0 || lo + len > nnz_total) return false;
+  *base = lo;
+  *count = len;
+  return true;
+}
+// a stored graph weight that counts: positive and finite
+__device__ __forceinline__ bool valid_weight(double w) { return w > 0.0 && w <= DBL_MAX; }
+// an index the caller supplied, read as the nearest one in [0, n)
+__device__ __forceinline__ int clamp_index(int v, int n) { return v < 0 ? 0 : (v >= n ? n - 1 : v); }
+// the splitmix64 step: the counter-based generator of every stage that draws
+__host__ __device__ __forceinline__ u64 mix64(u64 x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
 }
 
 // ---- LDS-DMA: every lane fetches 16 (glds4: 4) bytes; the wave's bytes land lane-linear at the wave-uniform LDS byte

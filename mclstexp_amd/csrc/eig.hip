@@ -78,27 +78,10 @@ __host__ EigWork eig_carve(void* work, long long S, long long sum_m, long long k
   return w;
 }
 
-// the splitmix64 step (csrc/umap.hip's um_mix)
-__device__ __forceinline__ u64 eg_mix(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 // start value of element (row, column) in [-1, 1): independent of the slide
 __device__ __forceinline__ double eg_start(int r, int c) {
-  const u64 h = eg_mix(((u64)(unsigned)r << 32) | (u64)(unsigned)c);
+  const u64 h = mix64(((u64)(unsigned)r << 32) | (u64)(unsigned)c);
   return (double)(h >> 11) * 0x1p-52 - 1.0;
-}
-
-// sum over the 256 threads in a fixed order: the butterfly inside each wave, then wave 0 + 1 + 2 + 3.  ``slot`` (4 doubles
-// of LDS) must not be reused before the reduction after the next one has begun: callers alternate two slots.
-__device__ __forceinline__ double eg_block_sum(double x, double* slot) {
-  x = wave_sum(x);
-  if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = x;
-  __syncthreads();
-  return ((slot[0] + slot[1]) + slot[2]) + slot[3];
 }
 
 // ------------------------------------------------------------------------------------------------------------- setup
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(EG_THREADS) void eig_house_kernel(double* __restric
   const double alpha = row[0];              // read by every thread before the barrier: thread 0 stores v_0 = 1 there
   double ss = 0.0;
   for (int i = 1 + tid; i < n; i += EG_THREADS) ss += row[i] * row[i];
-  ss = eg_block_sum(ss, slot);
+  ss = block_sum4<false>(ss, slot);
   const double xnorm = sqrt(ss);
   if (tid == 0) {
     w.d[o + j] = A[(long long)j * ms + j];
@@ -257,7 +240,7 @@ __global__ __launch_bounds__(EG_THREADS) void eig_rank2_kernel(double* __restric
   const double* p = w.p + o;
   double dot = 0.0;
   for (int c = threadIdx.x; c < n; c += EG_THREADS) dot += p[c] * v[c];
-  dot = eg_block_sum(dot, slot);
+  dot = block_sum4<false>(dot, slot);
   const double half = 0.5 * t * dot;
   const int lane = threadIdx.x & 63;
   const int r0 = blockIdx.x * EG_ROWS + (threadIdx.x >> 6) * EG_WROWS;
@@ -307,7 +290,7 @@ __global__ __launch_bounds__(64) void eig_bisect_kernel(int k, double* __restric
     e2max = fmax(e2max, hi * hi);
   }
 #pragma unroll
-  for (int x = 32; x > 0; x >>= 1) {
+  for (int x = 32; x > 0; x >>= 1) {   // wave_min / wave_max written out: three calls change this kernel's code
     gl = fmin(gl, __shfl_xor(gl, x, 64));
     gu = fmax(gu, __shfl_xor(gu, x, 64));
     e2max = fmax(e2max, __shfl_xor(e2max, x, 64));
@@ -483,7 +466,7 @@ __global__ __launch_bounds__(EG_THREADS) void eig_ortho_kernel(int k, EigWork w)
           zc[t] = r < ms ? z[(long long)r * k + c] : 0.0;
           dot = fma(zc[t], y[t], dot);
         }
-        dot = eg_block_sum(dot, slot[turn]);
+        dot = block_sum4<false>(dot, slot[turn]);
         turn ^= 1;
 #pragma unroll
         for (int t = 0; t < PER; ++t) y[t] -= dot * zc[t];
@@ -491,7 +474,7 @@ __global__ __launch_bounds__(EG_THREADS) void eig_ortho_kernel(int k, EigWork w)
     double ss = 0.0;
 #pragma unroll
     for (int t = 0; t < PER; ++t) ss = fma(y[t], y[t], ss);
-    ss = eg_block_sum(ss, slot[turn]);
+    ss = block_sum4<false>(ss, slot[turn]);
     turn ^= 1;
     const double nrm = sqrt(ss);
 #pragma unroll
@@ -558,7 +541,7 @@ __global__ __launch_bounds__(64) void eig_cert_reduce_kernel(int k, double* __re
   // a NaN anywhere must survive the maximum: fmax drops it, so it is carried as a flag
   int nan = (r != r) || (dv != dv);
 #pragma unroll
-  for (int x = 32; x > 0; x >>= 1) {
+  for (int x = 32; x > 0; x >>= 1) {   // wave_max written out: calls beside the flag's loop change this kernel's code
     r = fmax(r, __shfl_xor(r, x, 64));
     dv = fmax(dv, __shfl_xor(dv, x, 64));
     nan |= __shfl_xor(nan, x, 64);
@@ -600,7 +583,7 @@ __global__ __launch_bounds__(EG_THREADS) void eig_back_kernel(const double* __re
     const int q0 = j + 1 + ((tid - (j + 1)) & (EG_THREADS - 1));
     double dot = 0.0;
     for (int q = q0; q < ms; q += EG_THREADS) dot = fma(v[q], zl[q], dot);
-    dot = eg_block_sum(dot, slot[turn]);
+    dot = block_sum4<false>(dot, slot[turn]);
     turn ^= 1;
     const double f = t * dot;
     for (int q = q0; q < ms; q += EG_THREADS) zl[q] -= f * v[q];

@@ -30,14 +30,7 @@ constexpr int HM_MAX_B = 31;
 constexpr int HM_MAX_D = 1 << 22;   // columns ride on grid.y (64 or 256 per workgroup)
 constexpr int HM_SUM_THREADS = 128;
 
-__device__ __forceinline__ double hm_wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
-// batch[n] and order[i] come from the caller: an entry outside its range is read as the nearest valid one
-__device__ __forceinline__ int hm_clamp(int v, int hi) { return v < 0 ? 0 : (v >= hi ? hi - 1 : v); }
+// batch[n] and order[i] come from the caller: an entry outside its range is read as the nearest valid one (clamp_index)
 
 // ------------------------------------------------------------------------------------------------------- normalise
 // one wave per row; lanes stride the columns, fixed butterfly
@@ -57,7 +50,7 @@ __global__ __launch_bounds__(256) void hm_normalize_kernel(const T* z, long long
       nan |= v != v;
       mx = fmax(mx, v);
     }
-    mx = hm_wave_max(mx);
+    mx = wave_max(mx);
     if (__any(nan)) mx = NAN;
   }
   double ss = 0.0;
@@ -209,7 +202,7 @@ __global__ __launch_bounds__(256) void hm_softmax_kernel(const double* __restric
   const int ka = lane, kb = lane + 64;
   const double va = ka < K ? -dr[ka] / sigma : -INFINITY;
   const double vb = kb < K ? -dr[kb] / sigma : -INFINITY;
-  const double mx = hm_wave_max(fmax(va, vb));
+  const double mx = wave_max(fmax(va, vb));
   double ea = ka < K ? exp(va - mx) : 0.0, eb = kb < K ? exp(vb - mx) : 0.0;
   if (normalize) {
     const double s = wave_sum(ea + eb);
@@ -234,10 +227,10 @@ __global__ __launch_bounds__(HM_SUM_THREADS) void hm_block_sums_kernel(const dou
   for (int b = 0; b <= B; ++b) sh[b][tid] = 0.0;
   double tot = 0.0;
   for (int i = tid; i < len; i += HM_SUM_THREADS) {
-    const int n = order ? hm_clamp(order[start + i], N) : start + i;
+    const int n = order ? clamp_index(order[start + i], N) : start + i;
     const double v = R[(long long)n * K + k];
     tot += v;
-    sh[hm_clamp(batch[n], B)][tid] += v;
+    sh[clamp_index(batch[n], B)][tid] += v;
   }
   sh[B][tid] = tot;
   __syncthreads();
@@ -271,8 +264,8 @@ __global__ __launch_bounds__(256) void hm_block_cells_kernel(double* __restrict_
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= len) return;
-  const int n = hm_clamp(order[start + i], N);
-  const int b = hm_clamp(batch[n], B);
+  const int n = clamp_index(order[start + i], N);
+  const int b = clamp_index(batch[n], B);
   const double th = theta[b];
   const int ka = lane, kb = lane + 64;
   const int kac = ka < K ? ka : K - 1, kbc = kb < K ? kb : K - 1;
@@ -298,7 +291,7 @@ __global__ __launch_bounds__(256) void hm_objective_kernel(const double* __restr
   for (int r = 0; r < 16; ++r) {
     const int n = blockIdx.x * 64 + w * 16 + r;
     if (n >= N) break;
-    const int b = hm_clamp(batch[n], B);
+    const int b = clamp_index(batch[n], B);
     const double th = theta[b];
     for (int k = lane; k < K; k += 64) {
       const double rv = R[(long long)n * K + k];
@@ -515,19 +508,17 @@ __global__ __launch_bounds__(256) void hm_lloyd_mean_kernel(const double* __rest
 }
 
 // ------------------------------------------------------------------------------------------------------ host side
-inline int hm_ceil(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 // the cut of N for an M x d output: a function of the shapes alone
 inline void hm_slices(int N, int M, int d, int* slices, int* slice_len) {
-  const long long tiles = (long long)hm_ceil(M, 64) * hm_ceil(d, 64);
+  const long long tiles = (long long)ceil_div(M, 64) * ceil_div(d, 64);
   long long want = (1024 + tiles - 1) / tiles;
-  const long long most = hm_ceil(N, 256);
+  const long long most = ceil_div(N, 256);
   if (want > most) want = most;
   if (want < 1) want = 1;
-  int len = hm_ceil(N, want);
+  int len = ceil_div(N, want);
   len = (len + 3) / 4 * 4;
   *slice_len = len;
-  *slices = hm_ceil(N, len);
+  *slices = ceil_div(N, len);
 }
 
 inline int hm_limits(long long N, int K, int B) {
@@ -543,12 +534,12 @@ int hm_centroids_launch(const double* R, const int* labels, const double* X, con
   hm_slices(N, M, d, &slices, &len);
   double* dst = slices == 1 ? out : work;
   MCL_CLEAR_ERROR();
-  hipLaunchKernelGGL(hm_centroid_kernel<MODE>, dim3(hm_ceil(d, 64), hm_ceil(M, 64), slices), dim3(256), 0, st, R, labels, X,
+  hipLaunchKernelGGL(hm_centroid_kernel<MODE>, dim3(ceil_div(d, 64), ceil_div(M, 64), slices), dim3(256), 0, st, R, labels, X,
                      batch, N, K, d, G, len, dst);
   MCL_CHECK_LAUNCH();
   if (slices > 1) {
     const long long MD = (long long)M * d;
-    hipLaunchKernelGGL(hm_merge_kernel, dim3(hm_ceil(MD, 256)), dim3(256), 0, st, work, slices, MD, out);
+    hipLaunchKernelGGL(hm_merge_kernel, dim3(ceil_div(MD, 256)), dim3(256), 0, st, work, slices, MD, out);
     MCL_CHECK_LAUNCH();
   }
   return MCL_OK;
@@ -558,10 +549,10 @@ int hm_normalize_launch(const void* z, long long ld, int dtype, int N, int d, in
                         hipStream_t st) {
   MCL_CLEAR_ERROR();
   if (dtype == 0)
-    hipLaunchKernelGGL(hm_normalize_kernel<float>, dim3(hm_ceil(N, 4)), dim3(256), 0, st, (const float*)z, ld, N, d, by_max,
+    hipLaunchKernelGGL(hm_normalize_kernel<float>, dim3(ceil_div(N, 4)), dim3(256), 0, st, (const float*)z, ld, N, d, by_max,
                        z64, zc);
   else
-    hipLaunchKernelGGL(hm_normalize_kernel<double>, dim3(hm_ceil(N, 4)), dim3(256), 0, st, (const double*)z, ld, N, d,
+    hipLaunchKernelGGL(hm_normalize_kernel<double>, dim3(ceil_div(N, 4)), dim3(256), 0, st, (const double*)z, ld, N, d,
                        by_max, z64, zc);
   MCL_CHECK_LAUNCH();
   return MCL_OK;
@@ -569,8 +560,8 @@ int hm_normalize_launch(const void* z, long long ld, int dtype, int N, int d, in
 
 int hm_dist_launch(const double* Zc, const double* Y, int N, int K, int d, int raw, double* D, hipStream_t st) {
   MCL_CLEAR_ERROR();
-  const dim3 grid(hm_ceil(N, 16)), block(64);
-  switch (hm_ceil(K, 16)) {
+  const dim3 grid(ceil_div(N, 16)), block(64);
+  switch (ceil_div(K, 16)) {
 #define HM_DIST_CASE(T) \
   case T: hipLaunchKernelGGL(hm_dist_kernel<T>, grid, block, 0, st, Zc, Y, N, K, d, raw, D); break;
     HM_DIST_CASE(1) HM_DIST_CASE(2) HM_DIST_CASE(3) HM_DIST_CASE(4) HM_DIST_CASE(5) HM_DIST_CASE(6) HM_DIST_CASE(7)
@@ -595,7 +586,7 @@ int64_t mcl_harmony_workspace_doubles(int32_t N, int32_t K, int32_t d, int32_t B
     const long long need = slices > 1 ? (long long)slices * K * G * d : 0;
     if (need > most) most = need;
   }
-  const long long obj = 3ll * hm_ceil(N, 64);
+  const long long obj = 3ll * ceil_div(N, 64);
   return most > obj ? most : obj;
 }
 
@@ -628,7 +619,7 @@ int mcl_harmony_softmax(const double* D, int32_t N, int32_t K, double sigma, int
   if (!D || !out || N <= 0 || K <= 0 || !(sigma > 0.0)) return MCL_EINVAL;
   if (hm_limits(N, K, 0) != MCL_OK) return MCL_EUNSUPPORTED;
   MCL_CLEAR_ERROR();
-  hipLaunchKernelGGL(hm_softmax_kernel, dim3(hm_ceil(N, 4)), dim3(256), 0, mcl_stream(stream), D, N, K, sigma, normalize,
+  hipLaunchKernelGGL(hm_softmax_kernel, dim3(ceil_div(N, 4)), dim3(256), 0, mcl_stream(stream), D, N, K, sigma, normalize,
                      out);
   MCL_CHECK_LAUNCH();
   return MCL_OK;
@@ -660,7 +651,7 @@ int mcl_harmony_update_block(double* R, const double* S, const int32_t* batch, c
     const int len = base + (blk < extra ? 1 : 0);
     hipLaunchKernelGGL(hm_block_sums_kernel, dim3(K), dim3(HM_SUM_THREADS), 0, st, R, batch, order, start, len, N, K, B, Pr, -1,
                        E, O);
-    hipLaunchKernelGGL(hm_block_cells_kernel, dim3(hm_ceil(len, 4)), dim3(256), 0, st, R, S, batch, order, start, len, N, K, B,
+    hipLaunchKernelGGL(hm_block_cells_kernel, dim3(ceil_div(len, 4)), dim3(256), 0, st, R, S, batch, order, start, len, N, K, B,
                        theta, E, O);
     hipLaunchKernelGGL(hm_block_sums_kernel, dim3(K), dim3(HM_SUM_THREADS), 0, st, R, batch, order, start, len, N, K, B, Pr, 1,
                        E, O);
@@ -675,7 +666,7 @@ int mcl_harmony_objective(const double* R, const double* D, const int32_t* batch
   if (!R || !D || !batch || !E || !O || !theta || !work || !out3 || N <= 0 || K <= 0 || B <= 0) return MCL_EINVAL;
   if (hm_limits(N, K, B) != MCL_OK) return MCL_EUNSUPPORTED;
   hipStream_t st = mcl_stream(stream);
-  const int nwg = hm_ceil(N, 64);
+  const int nwg = ceil_div(N, 64);
   MCL_CLEAR_ERROR();
   hipLaunchKernelGGL(hm_objective_kernel, dim3(nwg), dim3(256), 0, st, R, D, batch, E, O, theta, N, K, B, work);
   hipLaunchKernelGGL(hm_objective_final_kernel, dim3(1), dim3(256), 0, st, work, nwg, sigma, out3);
@@ -688,7 +679,7 @@ int mcl_harmony_ridge(const double* O, const double* M, const double* lamb, int3
   if (!O || !M || !lamb || !W || K <= 0 || B <= 0 || d <= 0) return MCL_EINVAL;
   if (hm_limits(1, K, B) != MCL_OK || d > HM_MAX_D) return MCL_EUNSUPPORTED;
   MCL_CLEAR_ERROR();
-  hipLaunchKernelGGL(hm_ridge_kernel, dim3(K, hm_ceil(d, 256)), dim3(256), 0, mcl_stream(stream), O, M, lamb, K, B, d, W);
+  hipLaunchKernelGGL(hm_ridge_kernel, dim3(K, ceil_div(d, 256)), dim3(256), 0, mcl_stream(stream), O, M, lamb, K, B, d, W);
   MCL_CHECK_LAUNCH();
   return MCL_OK;
 }
@@ -698,7 +689,7 @@ int mcl_harmony_apply(const double* Z, const double* R, const double* W, const i
   if (!Z || !R || !W || !batch || !out || N <= 0 || K <= 0 || B <= 0 || d <= 0) return MCL_EINVAL;
   if (hm_limits(N, K, B) != MCL_OK || d > HM_MAX_D) return MCL_EUNSUPPORTED;
   MCL_CLEAR_ERROR();
-  hipLaunchKernelGGL(hm_apply_kernel, dim3(hm_ceil(N, 16), hm_ceil(d, 64)), dim3(64), 0, mcl_stream(stream), Z, R, W, batch, N,
+  hipLaunchKernelGGL(hm_apply_kernel, dim3(ceil_div(N, 16), ceil_div(d, 64)), dim3(64), 0, mcl_stream(stream), Z, R, W, batch, N,
                      K, B, d, out);
   MCL_CHECK_LAUNCH();
   return MCL_OK;
@@ -716,7 +707,7 @@ int mcl_harmony_lloyd(const double* Zc, int32_t N, int32_t K, int32_t d, const i
   for (int it = 0; it < iters; ++it) {
     int rc = hm_dist_launch(Zc, Y, N, K, d, 1, products, st);
     if (rc != MCL_OK) return rc;
-    hipLaunchKernelGGL(hm_label_kernel, dim3(hm_ceil(N, 4)), dim3(256), 0, st, products, N, K, labels);
+    hipLaunchKernelGGL(hm_label_kernel, dim3(ceil_div(N, 4)), dim3(256), 0, st, products, N, K, labels);
     MCL_CHECK_LAUNCH();
     rc = hm_centroids_launch<2>(nullptr, labels, Zc, nullptr, N, K, d, 1, work, sums, st);
     if (rc != MCL_OK) return rc;

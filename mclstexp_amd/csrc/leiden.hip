@@ -102,6 +102,8 @@ struct ld_args {
 };
 
 // ---------------------------------------------------------------------------------------------------------- helpers
+// segment_span and segment_entries (device.h) with A's fields read inside the test, not ahead of it: a call to either
+// reads them first and changes the code of this file's kernels
 __device__ __forceinline__ bool ld_segment(const ld_args& A, int s, long long* o, int* n0) {
   const long long lo = A.off[s], len = A.off[s + 1] - lo;
   if (lo < 0 || len < 2 || len > A.max_n || lo + len > A.rows) return false;
@@ -143,13 +145,7 @@ __device__ __forceinline__ void ld_row(const ld_graph& g, long long o, int s, in
   *lo = ok ? base + a : 0;
   *hi = ok ? base + b : 0;
 }
-__device__ __forceinline__ bool ld_valid_weight(double w) { return w > 0.0 && w <= DBL_MAX; }
 
-__device__ __forceinline__ long long ld_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 __device__ __forceinline__ void ld_add(long long* p, long long v) {
   atomicAdd(reinterpret_cast<unsigned long long*>(p), (unsigned long long)v);
 }
@@ -247,10 +243,10 @@ __global__ __launch_bounds__(LD_THREADS) void ld_prepare_kernel(ld_args A, const
   if (ok)
     for (long long e = threadIdx.x; e < cap; e += LD_THREADS) {
       const double v = data[base + e];
-      if (ld_valid_weight(v)) m = fmax(m, v);
+      if (valid_weight(v)) m = fmax(m, v);
     }
 #pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) m = fmax(m, __shfl_xor(m, sh, 64));
+  for (int sh = 32; sh > 0; sh >>= 1) m = fmax(m, __shfl_xor(m, sh, 64));   // wave_max(m) written out: a call changes this kernel's code
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x != 0) return;
@@ -287,11 +283,11 @@ __global__ __launch_bounds__(64) void ld_quantise_kernel(ld_args A, const double
     const double v = data[e];
     const int j = A.indices[e];
     long long q = 0;
-    if (ld_valid_weight(v) && j >= 0 && j < n0 && j != i) q = (long long)rint(ldexp(v, shift));
+    if (valid_weight(v) && j >= 0 && j < n0 && j != i) q = (long long)rint(ldexp(v, shift));
     A.w.q0[e] = q;
     sum += q;
   }
-  sum = ld_wave_sum(sum);
+  sum = wave_sum(sum);
   if (lane == 0) {
     A.w.kk[0][o + i] = sum;
     int p = partition ? partition[o + i] : i;
@@ -310,7 +306,7 @@ __global__ __launch_bounds__(LD_THREADS) void ld_m2_kernel(ld_args A) {
   if (!ld_segment(A, s, &o, &n0)) return;
   long long sum = 0;
   for (int i = threadIdx.x; i < n0; i += LD_THREADS) sum += A.w.kk[0][o + i];
-  sum = ld_wave_sum(sum);
+  sum = wave_sum(sum);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -440,7 +436,7 @@ __global__ __launch_bounds__(64) void ld_tally_move_kernel(ld_args A, int begin)
     const int j = g.ix[e];
     if (j >= 0 && j < n && P[j] == own) in += g.qw[e];
   }
-  in = ld_wave_sum(in);
+  in = wave_sum(in);
   if (lane == 0) {
     ld_add(ld_sel(A.w.tot[0], A.w.tot[1], buf) + o + own, g.kk[o + i]);
     if (in) ld_add(&st->in_new, in);
@@ -554,7 +550,7 @@ __device__ __forceinline__ void ld_propose(const ld_args& A, const ld_graph& g, 
     acc.add(R[j], q);
     kS += q;
   }
-  kS = ld_wave_sum(kS);
+  kS = wave_sum(kS);
   acc.phase();
   double bg = -HUGE_VAL;
   int bc = INT_MAX;
@@ -653,8 +649,8 @@ __global__ __launch_bounds__(64) void ld_tally_refine_kernel(ld_args A, int begi
     if (R[j] == r) in += q;
     else if (P[j] == S) out += q;
   }
-  in = ld_wave_sum(in);
-  out = ld_wave_sum(out);
+  in = wave_sum(in);
+  out = wave_sum(out);
   if (lane == 0) {
     ld_add(ld_sel(A.w.totR[0], A.w.totR[1], buf) + o + r, g.kk[o + i]);
     atomicAdd(ld_sel(A.w.size[0], A.w.size[1], buf) + o + r, 1);
@@ -836,7 +832,7 @@ __global__ __launch_bounds__(LD_THREADS) void ld_agg_indptr_kernel(ld_args A) {
   int m = 0;
   for (int a = threadIdx.x; a < nn; a += LD_THREADS) m = max(m, rowcnt[a]);
 #pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) m = max(m, __shfl_xor(m, sh, 64));
+  for (int sh = 32; sh > 0; sh >>= 1) m = max(m, __shfl_xor(m, sh, 64));   // an int maximum: device.h has none
   if ((threadIdx.x & 63) == 0) longest[threadIdx.x >> 6] = m;
   // the start labels of the next level: the smallest node of the vertex's community; founders carry their node's
   const int cur = st->f[F_CUR];
@@ -913,7 +909,6 @@ __global__ __launch_bounds__(LD_THREADS) void ld_finish_rank_kernel(ld_args A, i
   }
 }
 
-int ld_ceil(long long a, long long b) { return (int)((a + b - 1) / b); }
 bool ld_finite(double v) { return v == v && v <= DBL_MAX && v >= -DBL_MAX; }
 
 // the checks every launching entry point shares, and the argument block of its kernels
@@ -941,7 +936,7 @@ int ld_make(const int64_t* indptr, const int32_t* indices, const int64_t* offset
 }
 
 void ld_level_begin(const ld_args& A, int n_cur, hipStream_t st) {
-  const dim3 per_vertex(ld_ceil(n_cur, LD_THREADS), A.S), per_wave(n_cur, A.S);
+  const dim3 per_vertex(ceil_div(n_cur, LD_THREADS), A.S), per_wave(n_cur, A.S);
   hipLaunchKernelGGL(ld_zero_move_kernel, per_vertex, dim3(LD_THREADS), 0, st, A, 1);
   hipLaunchKernelGGL(ld_tally_move_kernel, per_wave, dim3(64), 0, st, A, 1);
   hipLaunchKernelGGL(ld_q_move_kernel, dim3(A.S), dim3(LD_THREADS), 0, st, A, 1, 0);
@@ -985,7 +980,7 @@ int mcl_leiden_move_sweeps(int32_t count, int32_t level, int32_t n_cur, int32_t 
   if (rc != MCL_OK) return rc;
   if (count < 0 || n_cur < 1 || n_cur > max_n || max_sweeps < 1) return MCL_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 per_vertex(ld_ceil(n_cur, LD_THREADS), S), per_wave(n_cur, S);
+  const dim3 per_vertex(ceil_div(n_cur, LD_THREADS), S), per_wave(n_cur, S);
   MCL_CLEAR_ERROR();
   for (int t = 0; t < count; ++t) {
     hipLaunchKernelGGL(ld_zero_move_kernel, per_vertex, dim3(LD_THREADS), 0, st, A, 0);
@@ -1007,7 +1002,7 @@ int mcl_leiden_refine_rounds(int32_t begin, int32_t count, int32_t level, int32_
   if (rc != MCL_OK) return rc;
   if (count < 0 || n_cur < 1 || n_cur > max_n || max_rounds < 1) return MCL_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 per_vertex(ld_ceil(n_cur, LD_THREADS), S), per_wave(n_cur, S);
+  const dim3 per_vertex(ceil_div(n_cur, LD_THREADS), S), per_wave(n_cur, S);
   MCL_CLEAR_ERROR();
   if (begin) {
     hipLaunchKernelGGL(ld_zero_refine_kernel, per_vertex, dim3(LD_THREADS), 0, st, A, 1);
@@ -1034,7 +1029,7 @@ int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const
   if (rc != MCL_OK) return rc;
   if (n_cur < 1 || n_cur > max_n || max_levels < 1) return MCL_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 per_vertex(ld_ceil(n_cur, LD_THREADS), S);
+  const dim3 per_vertex(ceil_div(n_cur, LD_THREADS), S);
   MCL_CLEAR_ERROR();
   hipLaunchKernelGGL(ld_agg_number_kernel, dim3(S), dim3(LD_THREADS), 0, st, A, max_levels);
   hipLaunchKernelGGL(ld_agg_zero_kernel, per_vertex, dim3(LD_THREADS), 0, st, A);
@@ -1042,7 +1037,7 @@ int mcl_leiden_aggregate(int32_t level, int32_t n_cur, int32_t max_levels, const
   hipLaunchKernelGGL(ld_agg_rows_kernel, dim3(LD_DENSE), dim3(64), 0, st, A, 0);
   hipLaunchKernelGGL(ld_agg_indptr_kernel, dim3(S), dim3(LD_THREADS), 0, st, A);
   hipLaunchKernelGGL(ld_agg_rows_kernel, dim3(LD_DENSE), dim3(64), 0, st, A, 1);
-  hipLaunchKernelGGL(ld_agg_done_kernel, dim3(ld_ceil(S, LD_THREADS)), dim3(LD_THREADS), 0, st, A);
+  hipLaunchKernelGGL(ld_agg_done_kernel, dim3(ceil_div(S, LD_THREADS)), dim3(LD_THREADS), 0, st, A);
   A.level = level + 1;                                   // Q of the start partition of the next level
   ld_level_begin(A, n_cur, st);
   MCL_CHECK_LAUNCH();
@@ -1058,7 +1053,7 @@ int mcl_leiden_finish(int32_t source, int32_t final_labels, const int32_t* activ
   if (rc != MCL_OK) return rc;
   if (!canonical || (source != 0 && source != 1) || (final_labels && (!labels || !n_clusters))) return MCL_EINVAL;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const dim3 per_vertex(ld_ceil(max_n, LD_THREADS), S);
+  const dim3 per_vertex(ceil_div(max_n, LD_THREADS), S);
   MCL_CLEAR_ERROR();
   if (!final_labels)
     for (int stage = 0; stage < 3; ++stage)

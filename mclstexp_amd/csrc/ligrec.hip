@@ -55,12 +55,6 @@ inline long long lr_chunk(long long S, long long kmax, long long U, long long P)
   return c < 1 ? 1 : c;
 }
 
-__device__ __forceinline__ double lr_wave_total(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
 // The halving tree over the 64 lanes for W columns at once.  At a level that still holds more than one column the lanes with
 // bit o set keep the upper half of the columns and hand the lower half to their partner, the others the reverse: every lane
 // adds its own value of a column and its partner's (lanes l and l ^ o: the two numbers p[l] += p[l + o] adds), so each
@@ -93,21 +87,6 @@ __device__ __forceinline__ int lr_lane_column(int lane) {
   return col;
 }
 
-__device__ __forceinline__ int lr_wave_count(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
-// rows of slide s, 0 when its offsets break the caller's statements
-__device__ __forceinline__ int lr_slide_rows(const long long* __restrict__ offsets, int s, long long rows, int max_n,
-                                             long long* r0_out) {
-  const long long r0 = offsets[s], r1 = offsets[s + 1];
-  *r0_out = r0;
-  if (r0 < 0 || r1 - r0 < 2 || r1 > rows || r1 - r0 > max_n) return 0;
-  return (int)(r1 - r0);
-}
-
 // ---------------------------------------------------------------------------------------------------------- prepare
 __global__ __launch_bounds__(LR_THREADS) void lr_prepare_kernel(
     const long long* __restrict__ offsets, const int* __restrict__ labels, const int* __restrict__ kk, long long rows,
@@ -118,7 +97,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_prepare_kernel(
   __shared__ int bad_s;
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long r0;
-  const int ns = lr_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int K = kk[s];
   int* st = start + (long long)s * (kmax + 1);
   if (ns == 0 || K < 1 || K > kmax) {
@@ -190,7 +169,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_means_kernel(
   double* xs = reinterpret_cast<double*>(lr_lds);            // [n][C]: sorted position j, column q
   const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   long long r0;
-  const int ns = lr_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int K = kk[s];
   if (ns == 0 || K < 1 || K > kmax) return;
   const int* st = start + (long long)s * (kmax + 1);
@@ -273,7 +252,7 @@ __global__ __launch_bounds__(LR_THREADS) void lr_means_kernel(
       int nz = 0;
 #pragma unroll
       for (int j = 0; j < C; ++j) {
-        const int cj = lr_wave_count(cnt[j]);
+        const int cj = wave_sum(cnt[j]);
         if (j == q) nz = cj;
       }
       if (writer) {

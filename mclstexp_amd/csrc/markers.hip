@@ -249,7 +249,8 @@ __global__ __launch_bounds__(MK_MOM_THREADS) void marker_moments_kernel(
 }
 
 // ------------------------------------------------------------------------------------------------------------- ranks
-// the order-preserving integer image of a value; -0.0 and +0.0 share one key
+// the order-preserving integer image of a value; -0.0 and +0.0 share one key, unlike device.h's order_key (written through
+// it, order_key(v == 0 ? 0 : v), the code of this file's kernels changes)
 __device__ __forceinline__ unsigned mk_key(float v) {
   const unsigned u = v == 0.0f ? 0u : __float_as_uint(v);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);

@@ -32,19 +32,6 @@ constexpr double NB_SMOOTH_TOL = 1e-5;          // SMOOTH_K_TOLERANCE
 constexpr double NB_MIN_SCALE = 1e-3;           // MIN_K_DIST_SCALE
 constexpr int NB_SLOTS = NB_MAX_K / 64;         // entries of a row a lane holds
 
-inline int nb_ceil(int a, int b) { return (a + b - 1) / b; }
-
-// the segment of this workgroup: first row and rows.  False (for the whole workgroup) where the offsets the caller vouched
-// for do not fit the limits the launch was sized by: nothing is read or written then.
-__device__ __forceinline__ bool nb_segment(const long long* off, int s, int k, int max_n, long long rows, long long* o,
-                                           int* n) {
-  const long long lo = off[s], len = off[s + 1] - lo;
-  if (lo < 0 || len < 2 || len < k || len > max_n || lo + len > rows) return false;
-  *o = lo;
-  *n = (int)len;
-  return true;
-}
-
 // Exclusive prefix of v over the 256 threads in thread order and, in *total, the sum.  `ws` holds 4 ints; two barriers.
 __device__ __forceinline__ int nb_block_scan(int v, int* ws, int* total) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -98,7 +85,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_knn_kernel(const T* __restrict_
   int* misc = hist + NB_THREADS;               // 0..3 scan, 4 digit, 5 rank left, 6 winners
   long long o;
   int n;
-  if (!nb_segment(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
   const int i = blockIdx.x, tid = threadIdx.x;
   if (i >= n) return;
   if (tid < D) xi[tid] = (double)x[(o + i) * ld + tid];
@@ -177,12 +164,6 @@ __global__ __launch_bounds__(NB_THREADS) void nb_knn_kernel(const T* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------- smoothing
-__device__ __forceinline__ double nb_wave_min(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
-  return v;
-}
-
 // sum of e[1 .. k-1] in index order, the same in every lane; lane l holds entry 64 c + l in e[c]
 __device__ __forceinline__ double nb_ordered_sum(const double (&e)[NB_SLOTS], int first, int k) {
   double s = 0.0;
@@ -215,7 +196,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_smooth_kernel(const double* __r
     dl[c] = j < k ? d[j] : 0.0;
     if (dl[c] > 0.0) rho = fmin(rho, dl[c]);
   }
-  rho = nb_wave_min(rho);
+  rho = wave_min(rho);
   if (rho == INFINITY) rho = 0.0;
   const double total = nb_ordered_sum(dl, 0, k);
   double lo = 0.0, hi = INFINITY, mid = 1.0;
@@ -252,7 +233,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_floor_kernel(const long long* _
   __shared__ double red[4];
   long long o;
   int n;
-  if (!nb_segment(off, blockIdx.x, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.x, k, max_n, rows, &o, &n)) return;
   double s = 0.0;
   for (int i = threadIdx.x; i < n; i += NB_THREADS) s += rowsum[o + i];
   s = wave_sum(s);
@@ -306,7 +287,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_indegree_kernel(const int* __re
                                                                  long long rows, int k, int* __restrict__ indeg) {
   long long o;
   int n;
-  if (!nb_segment(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
   const int i = blockIdx.x, t = threadIdx.x;
   if (i >= n || t >= k) return;
   const int j = idx[(o + i) * k + t];
@@ -320,7 +301,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_scan_kernel(const long long* __
   __shared__ int ws[4];
   long long o;
   int n;
-  if (!nb_segment(off, blockIdx.x, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.x, k, max_n, rows, &o, &n)) return;
   int carry = 0;
   for (int base = 0; base < n; base += NB_THREADS) {
     const int i = base + threadIdx.x;
@@ -340,7 +321,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_reverse_kernel(const int* __res
                                                                 long long rows, int k, nb_work w) {
   long long o;
   int n;
-  if (!nb_segment(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.y, k, max_n, rows, &o, &n)) return;
   const int i = blockIdx.x, t = threadIdx.x;
   if (i >= n || t >= k) return;
   const int j = idx[(o + i) * k + t];
@@ -370,7 +351,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_union_kernel(const int* __restr
   long long o;
   int n;
   const int s = blockIdx.y;
-  if (!nb_segment(off, s, k, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, s, k, max_n, rows, &o, &n)) return;
   const int i = blockIdx.x, tid = threadIdx.x;
   if (i >= n) return;
   for (int j = tid; j < n; j += NB_THREADS) val[j] = -1.0;
@@ -433,7 +414,7 @@ __global__ __launch_bounds__(NB_THREADS) void nb_indptr_kernel(const long long* 
   long long o;
   int n;
   const int s = blockIdx.x;
-  if (!nb_segment(off, s, k, max_n, rows, &o, &n)) {
+  if (!segment_span(off, s, k, max_n, rows, &o, &n)) {
     if (threadIdx.x == 0) nnz[s] = -1;
     return;
   }
@@ -508,7 +489,7 @@ int mcl_knn_smooth(const double* knn_distances, const int64_t* offsets, int32_t 
   const long long* off = reinterpret_cast<const long long*>(offsets);
   double* rowsum = static_cast<double*>(work);
   MCL_CLEAR_ERROR();
-  hipLaunchKernelGGL(nb_smooth_kernel, dim3(nb_ceil(rows, 4)), dim3(NB_THREADS), 0, st, knn_distances, (long long)rows, k,
+  hipLaunchKernelGGL(nb_smooth_kernel, dim3(ceil_div(rows, 4)), dim3(NB_THREADS), 0, st, knn_distances, (long long)rows, k,
                      log2((double)k), rho, sigma, rowsum);
   hipLaunchKernelGGL(nb_floor_kernel, dim3(S), dim3(NB_THREADS), 0, st, off, max_n, (long long)rows, k, rowsum, rho, sigma);
   MCL_CHECK_LAUNCH();

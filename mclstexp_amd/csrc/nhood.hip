@@ -60,15 +60,6 @@ __host__ __device__ inline bool nh_staged(int n, int K, int kw) {
   return (long long)n * kw * 2 <= (long long)nh_budget(n) - (long long)nh_tile_rows(n, K) * K * NH_CELL_BYTES;
 }
 
-// rows of slide s, 0 when its offsets break the caller's statements
-__device__ __forceinline__ int nh_slide_rows(const long long* __restrict__ offsets, int s, long long rows, int max_n,
-                                             long long* r0_out) {
-  const long long r0 = offsets[s], r1 = offsets[s + 1];
-  *r0_out = r0;
-  if (r0 < 0 || r1 - r0 < 2 || r1 > rows || r1 - r0 > max_n) return 0;
-  return (int)(r1 - r0);
-}
-
 // the group that owns sorted position j: the last c < K with start_s[c] <= j (start_s ascending, start_s[0] = 0)
 __device__ __forceinline__ int nh_group_of(const int* start_s, int K, int j) {
   int lo = 0, hi = K;
@@ -85,7 +76,7 @@ __global__ __launch_bounds__(NH_C_THREADS) void nh_compact_kernel(
     const double* __restrict__ w, int kw, unsigned short* __restrict__ nbr16, int* __restrict__ status) {
   const int s = blockIdx.y;
   long long r0;
-  const int ns = nh_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int e = blockIdx.x * NH_C_THREADS + threadIdx.x;
   if (e >= ns * kw) return;
   const long long o = r0 * kw + e;
@@ -105,7 +96,7 @@ __global__ __launch_bounds__(NH_THREADS) void nh_counts_kernel(
   __shared__ int start_s[NH_MAX_K + 2];
   const int tile = blockIdx.x, z = blockIdx.y, Z = gridDim.y, s = blockIdx.z, tid = threadIdx.x;
   long long r0;
-  const int ns = nh_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int K = kk[s];
   if (ns == 0 || K < 1 || K > kmax) return;
   const int* st = start + (long long)s * (kmax + 1);
@@ -201,7 +192,7 @@ __global__ __launch_bounds__(NH_C_THREADS) void cc_gather_kernel(
     double* __restrict__ sorted, int* __restrict__ status) {
   const int s = blockIdx.y;
   long long r0;
-  const int ns = nh_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int K = kk[s];
   if (ns == 0 || K < 1 || K > kmax) return;
   const int n = min(max(start[(long long)s * (kmax + 1) + K], 0), ns);
@@ -225,7 +216,7 @@ __global__ __launch_bounds__(CC_TILE) void cc_counts_kernel(
   unsigned* hist_s = reinterpret_cast<unsigned*>(cc_lds);      // [group of i within the tile][t]: at most K groups
   const int s = blockIdx.z, tid = threadIdx.x;
   long long r0;
-  const int ns = nh_slide_rows(offsets, s, rows, max_n, &r0);
+  const int ns = segment_rows(offsets, s, rows, 2, max_n, &r0);
   const int K = kk[s];
   if (ns == 0 || K < 1 || K > kmax) return;
   const int* st = start + (long long)s * (kmax + 1);

@@ -48,18 +48,6 @@ struct SlideSet {  // device-resident arrays, one entry per slide (row_off: S + 
   const long long* row_off;
 };
 
-__device__ __forceinline__ int clamp_col(int c, int ncols) { return c < 0 ? 0 : (c >= ncols ? ncols - 1 : c); }
-
-// ---- order-preserving bit pattern of a double (no NaN): a < b <=> key(a) < key(b), -0.0 just below +0.0
-__device__ __forceinline__ u64 order_key(double v) {
-  const u64 b = (u64)__double_as_longlong(v);
-  return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double key_value(u64 k) {
-  const u64 b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-  return __longlong_as_double((long long)b);
-}
-
 // The value of descending rank k (0 = the largest) among the valid entries of v[0..n): the positive ones (POSITIVE) or the
 // non-NaN ones.  Exact: eight passes fix one byte of the key each.  Called by all FIN_THREADS threads with 0 <= k < the
 // number of valid entries; hist: FIN_THREADS ints, pick: 2 ints of LDS.
@@ -112,7 +100,7 @@ __global__ __launch_bounds__(LIB_WAVES * 64) void hvg_libsize_kernel(SlideSet sl
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const int g = g0 + 64 * u;
-      if (g < G) acc[u] += (double)x[clamp_col(map ? map[g] : g, nc)];
+      if (g < G) acc[u] += (double)x[clamp_index(map ? map[g] : g, nc)];
     }
   }
   const double a = wave_sum((acc[0] + acc[1]) + (acc[2] + acc[3]));
@@ -179,7 +167,7 @@ __global__ __launch_bounds__(MOM_WAVES * 64) void hvg_moments_kernel(SlideSet sl
   const int gc = g < G ? g : G - 1;  // lanes past G load gene G-1 and store nothing
   const int n = sl.rows[s];
   const long long ld = sl.ld[s];
-  const int c = clamp_col(colmaps ? colmaps[(long long)s * G + gc] : gc, sl.ncols[s]);
+  const int c = clamp_index(colmaps ? colmaps[(long long)s * G + gc] : gc, sl.ncols[s]);
   const T* col = static_cast<const T*>(sl.ptr[s]) + c;
   const double* f = fac + sl.row_off[s];
   constexpr int STEP = MOM_WAVES * MOM_UNROLL;
@@ -409,7 +397,7 @@ __global__ __launch_bounds__(256) void expr_matrices_kernel(SlideSet sl, const i
     double a = 0.0;
     if (row < n) {
       const T* xr = x + (long long)row * ld;
-      for (int k = lane; k < K; k += 64) a += (double)xr[clamp_col(sel[k], nc)];
+      for (int k = lane; k < K; k += 64) a += (double)xr[clamp_index(sel[k], nc)];
     }
     a = wave_sum(a);
     if (lane == 0) fac[r] = a != 0.0 ? (float)((double)rescale / a) : 0.f;  // an empty spot stays all-zero
@@ -417,7 +405,7 @@ __global__ __launch_bounds__(256) void expr_matrices_kernel(SlideSet sl, const i
   __syncthreads();
   for (int k0 = 0; k0 < K; k0 += 64) {
     const int k = k0 + lane;
-    const int c = clamp_col(k < K ? sel[k] : 0, nc);
+    const int c = clamp_index(k < K ? sel[k] : 0, nc);
     for (int rr = 0; rr < 16; ++rr) {
       const int r = w * 16 + rr;
       const int row = row0 + r;

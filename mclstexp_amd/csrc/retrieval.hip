@@ -38,16 +38,6 @@ __global__ __launch_bounds__(256) void l2_normalize_rows_kernel(const float* __r
   for (int c = lane; c < dim; c += 64) yr[c] = xr[c] / denom;
 }
 
-// larger float <=> larger key (NaN with the sign bit clear sorts above +inf, as torch.topk treats it)
-__device__ __forceinline__ unsigned f2key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k;
-  return __uint_as_float(u);
-}
-
 // append (key, idx) of the flagged lanes to sel[] through ONE LDS atomic per wave
 __device__ __forceinline__ void wave_append(bool flag, unsigned key, unsigned idx, unsigned long long* sel,
                                             unsigned* counter, unsigned cap) {
@@ -86,12 +76,12 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_rows_kernel(const float* __
   // ---- pass 0: key range of the row
   unsigned kmin = 0xFFFFFFFFu, kmax = 0u;
   for (int i = tid; i < n; i += TOPK_THREADS) {
-    const unsigned key = f2key(row[i]);
+    const unsigned key = order_key(row[i]);
     kmin = min(kmin, key);
     kmax = max(kmax, key);
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {   // unsigned minimum and maximum: device.h has neither
     kmin = min(kmin, (unsigned)__shfl_xor((int)kmin, o, 64));
     kmax = max(kmax, (unsigned)__shfl_xor((int)kmax, o, 64));
   }
@@ -120,7 +110,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_rows_kernel(const float* __
     __syncthreads();
     unsigned cur = 0xFFFFFFFFu, run = 0;
     for (int i = tid; i < n; i += TOPK_THREADS) {
-      const unsigned key = f2key(row[i]);
+      const unsigned key = order_key(row[i]);
       if (((unsigned long long)key >> s) == pref) {
         const unsigned d = (key >> s2) & dmask;
         if (d != cur) {
@@ -174,7 +164,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_rows_kernel(const float* __
     unsigned key = 0;
     bool win = false, tie = false;
     if (i < n) {
-      key = f2key(row[i]);
+      key = order_key(row[i]);
       const unsigned long long hi = (unsigned long long)key >> s;
       win = hi > pref;
       tie = (hi == pref) && (inbin == need);
@@ -191,7 +181,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_rows_kernel(const float* __
       unsigned key = 0;
       bool tie = false;
       if (i < n) {
-        key = f2key(row[i]);
+        key = order_key(row[i]);
         tie = ((unsigned long long)key >> s) == pref;
       }
       const unsigned long long mask = __ballot(tie);
@@ -237,7 +227,7 @@ __global__ __launch_bounds__(TOPK_THREADS) void topk_rows_kernel(const float* __
   }
   for (int i = tid; i < k; i += TOPK_THREADS) {
     const unsigned long long c = sel[i];
-    values[(long long)blockIdx.x * k + i] = key2f((unsigned)(c >> 32));
+    values[(long long)blockIdx.x * k + i] = key_value((unsigned)(c >> 32));
     indices[(long long)blockIdx.x * k + i] = (long long)(0xFFFFFFFFu - (unsigned)c);
   }
 }

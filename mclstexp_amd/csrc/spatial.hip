@@ -68,22 +68,9 @@ __host__ __device__ inline int sp_pow2ceil(int n) {
   while (p < n) p <<= 1;
   return p;
 }
-// the splitmix64 step (csrc/umap.hip's um_mix)
-__host__ __device__ __forceinline__ u64 sp_mix(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
 
-__device__ __forceinline__ double sp_wave_total(double v) {
-#pragma clang fp contract(off)
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-// rows of slide s, 0 when its offsets break the caller's statements
+// rows of slide s, 0 when its offsets break the caller's statements: segment_rows (device.h) with r1 < r0 tested ahead of
+// the subtraction and the terms in another order; the shared form changes the code of this file's kernels
 __device__ __forceinline__ int sp_slide_rows(const long long* __restrict__ offsets, int s, long long rows, int min_n, int max_n,
                                              long long* r0_out) {
   const long long r0 = offsets[s], r1 = offsets[s + 1];
@@ -249,9 +236,9 @@ __global__ __launch_bounds__(SP_LANES) void sp_consts_kernel(
     a1 = a1 + s1;
     a2 = a2 + sq;
   }
-  a0 = sp_wave_total(a0);
-  a1 = sp_wave_total(a1);
-  a2 = sp_wave_total(a2);
+  a0 = wave_sum(a0);
+  a1 = wave_sum(a1);
+  a2 = wave_sum(a2);
   if ((r & 63) == 0) { red[0][r >> 6] = a0; red[1][r >> 6] = a1; red[2][r >> 6] = a2; }
   __syncthreads();
   if (r < 3) {
@@ -271,9 +258,9 @@ __global__ __launch_bounds__(SP_SORT_THREADS) void sp_perm_kernel(const long lon
   const int n = sp_slide_rows(offsets, s, rows, 2, max_n, &r0);
   if (n == 0) return;
   const int P2 = sp_pow2ceil(n);
-  const u64 h = sp_mix(sp_mix(seed) ^ (u64)p);
+  const u64 h = mix64(mix64(seed) ^ (u64)p);
   for (int e = tid; e < P2; e += SP_SORT_THREADS)
-    keys[e] = e < n ? ((sp_mix(h + (u64)e) & ~0x3FFFull) | (u64)e) : ~0ull;
+    keys[e] = e < n ? ((mix64(h + (u64)e) & ~0x3FFFull) | (u64)e) : ~0ull;
   __syncthreads();
   for (int k2 = 2; k2 <= P2; k2 <<= 1) {
     for (int j = k2 >> 1; j > 0; j >>= 1) {
@@ -338,7 +325,7 @@ __global__ __launch_bounds__(SP_STAT_THREADS) void sp_stat_kernel(
     double a = 0.0;
     if (q < C)
       for (int i = r; i < n; i += SP_LANES) a = a + zs[i * C + q];
-    a = sp_wave_total(a);
+    a = wave_sum(a);
     if (lane == 0) part[0][grp][wg][0] = a;
     __syncthreads();
     if (tid < SP_GROUPS && q0 + tid < C)
@@ -360,7 +347,7 @@ __global__ __launch_bounds__(SP_STAT_THREADS) void sp_stat_kernel(
         const double sq = z * z;
         a = a + sq;
       }
-    a = sp_wave_total(a);
+    a = wave_sum(a);
     if (lane == 0) part[0][grp][wg][0] = a;
     __syncthreads();
     if (tid < SP_GROUPS && q0 + tid < C)
@@ -422,7 +409,7 @@ __global__ __launch_bounds__(SP_STAT_THREADS) void sp_stat_kernel(
     double (*buf)[4][2 * C] = part[it & 1];
 #pragma unroll
     for (int q = 0; q < C; ++q) {
-      const double tI = sp_wave_total(aI[q]), tC = sp_wave_total(aC[q]);
+      const double tI = wave_sum(aI[q]), tC = wave_sum(aC[q]);
       if (lane == 0) { buf[grp][wg][q] = tI; buf[grp][wg][C + q] = tC; }
     }
     __syncthreads();                                         // (the other buffer is written next: one barrier per round)

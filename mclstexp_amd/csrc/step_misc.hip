@@ -266,12 +266,6 @@ __global__ __launch_bounds__(256) void scale2_kernel(const float* __restrict__ a
 // (/root/reference/model.py:25-29,156,164; the reference never activates it: model.py:217 hard-codes 0.).  The mask comes
 // from a counter-based generator (one 64-bit mix of (seed, element index) per element: reproducible for a given seed, no
 // state), is kept as one byte per element for the backward, and kept elements are scaled by 1 / (1 - p).
-__device__ __forceinline__ unsigned long long mix64(unsigned long long z) {
-  z += 0x9E3779B97F4A7C15ull;
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  return z ^ (z >> 31);
-}
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                           unsigned char* __restrict__ mask, long long n, float p, float scale,
                                                           unsigned long long seed) {

@@ -36,16 +36,6 @@ constexpr int TS_CHUNK = 2048;                  // y_j staged per pass: 32 KiB
 constexpr int TS_ACC = 7;                       // per-row sums: A0 A1 R0 R1 S K sum p'
 constexpr int TS_PARAMS = 5;                    // per segment: exaggeration, momentum, learning rate, active, reset
 
-// the sum over a 256-thread workgroup in a fixed order: butterfly inside each wave, then the four waves in index order.
-// Every thread returns the same value.  `red` holds 4 doubles; two barriers.
-__device__ __forceinline__ double ts_block_sum(double v, double* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
-
 // the segment of this workgroup: first row, rows, first pair.  False (for the whole workgroup) where the offsets the
 // caller vouched for do not fit the limits the launch was sized by: nothing is read or written then.
 __device__ __forceinline__ bool ts_segment(const long long* off, const long long* poff, int s, int max_n, long long pairs,
@@ -91,8 +81,8 @@ __global__ __launch_bounds__(TS_THREADS) void ts_affinity_kernel(const T* __rest
       s += e;
       t = fma(d, e, t);
     }
-    s = ts_block_sum(s, red[0]);
-    t = ts_block_sum(t, red[1]);
+    s = block_sum4<true>(s, red[0]);
+    t = block_sum4<true>(t, red[1]);
     if (s == 0.0) s = TS_ZERO_SUM;
     sum = s;
     const double diff = log(s) + beta * t / s - log_perplexity;    // the same in every thread
@@ -154,7 +144,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_rowsum_kernel(const long long* 
   if (lane == 0) rowsum[o + i] = s;
 }
 
-// one workgroup per segment: the sum of its row sums (threads stride the rows, then ts_block_sum), floored at eps
+// one workgroup per segment: the sum of its row sums (threads stride the rows, then block_sum4), floored at eps
 __global__ __launch_bounds__(TS_THREADS) void ts_segsum_kernel(const long long* __restrict__ off, int max_n,
                                                                const double* __restrict__ rowsum,
                                                                double* __restrict__ segsum) {
@@ -163,7 +153,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_segsum_kernel(const long long* 
   if (len < 2 || len > max_n) return;
   double s = 0.0;
   for (int i = threadIdx.x; i < (int)len; i += TS_THREADS) s += rowsum[o + i];
-  s = ts_block_sum(s, red);
+  s = block_sum4<true>(s, red);
   if (threadIdx.x == 0) segsum[blockIdx.x] = fmax(s, TS_EPS);
 }
 
@@ -265,7 +255,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_finish_kernel(const long long* 
   const int n = (int)len;
   double q = 0.0;
   for (int i = threadIdx.x; i < n; i += TS_THREADS) q += rowacc[4 * rows + o + i];
-  q = ts_block_sum(q, red[0]);
+  q = block_sum4<true>(q, red[0]);
   if (want_kl) {
     // sum K_i and log(sum Q) sum p' are each several times the KL they leave, so one rounding of either is ulps of the
     // result.  The rows' own shares K_i + log(sum Q) sum_j p'_ij are summed instead, with log(sum Q) = e ln2 + log(m),
@@ -282,7 +272,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_finish_kernel(const long long* 
       const double ps = rowacc[6 * rows + o + i];
       k += fma(ps, l_hi, rowacc[5 * rows + o + i]) + ps * l_lo;
     }
-    k = ts_block_sum(k, red[1]);
+    k = block_sum4<true>(k, red[1]);
     if (threadIdx.x == 0) kl[s] = k;
   }
   for (int i = threadIdx.x; i < n; i += TS_THREADS) {
@@ -318,7 +308,7 @@ __global__ __launch_bounds__(TS_THREADS) void ts_update_kernel(const double* __r
     Y[e] += un;
     nrm = fma(gg, gg, nrm);
   }
-  nrm = ts_block_sum(nrm, red);
+  nrm = block_sum4<true>(nrm, red);
   if (threadIdx.x == 0) grad_norm2[s] = nrm;
 }
 
@@ -329,8 +319,6 @@ int ts_limits(int S, long long rows, int min_n, int max_n, long long pairs) {
     return MCL_EINVAL;
   return MCL_OK;
 }
-
-inline int ts_ceil(int a, int b) { return (a + b - 1) / b; }
 
 }  // namespace
 
@@ -372,15 +360,15 @@ int mcl_tsne_affinities(const void* x, int64_t ld, int32_t dtype, int32_t D, con
     hipLaunchKernelGGL(ts_affinity_kernel<double>, dim3(max_n, S), dim3(TS_THREADS), lds, st, (const double*)x,
                        (long long)ld, D, off, poff, max_n, (long long)pairs, lp, float32_distances, P, beta);
   MCL_CHECK_LAUNCH();
-  const int tiles = ts_ceil(max_n, TS_TILE);
+  const int tiles = ceil_div(max_n, TS_TILE);
   double* rowsum = work;
   double* segsum = work + rows;
   hipLaunchKernelGGL(ts_symmetrize_kernel, dim3(tiles, tiles, S), dim3(TS_THREADS), 0, st, off, poff, max_n,
                      (long long)pairs, P);
-  hipLaunchKernelGGL(ts_rowsum_kernel, dim3(ts_ceil(max_n, 4), S), dim3(TS_THREADS), 0, st, off, poff, max_n,
+  hipLaunchKernelGGL(ts_rowsum_kernel, dim3(ceil_div(max_n, 4), S), dim3(TS_THREADS), 0, st, off, poff, max_n,
                      (long long)pairs, P, rowsum);
   hipLaunchKernelGGL(ts_segsum_kernel, dim3(S), dim3(TS_THREADS), 0, st, off, max_n, rowsum, segsum);
-  hipLaunchKernelGGL(ts_normalize_kernel, dim3(ts_ceil(max_n, 4), S), dim3(TS_THREADS), 0, st, off, poff, max_n,
+  hipLaunchKernelGGL(ts_normalize_kernel, dim3(ceil_div(max_n, 4), S), dim3(TS_THREADS), 0, st, off, poff, max_n,
                      (long long)pairs, segsum, P);
   MCL_CHECK_LAUNCH();
   return MCL_OK;
@@ -396,7 +384,7 @@ int mcl_tsne_gradient(const double* P, const int64_t* pair_offsets, const double
   hipStream_t st = mcl_stream(stream);
   const long long* off = reinterpret_cast<const long long*>(offsets);
   const long long* poff = reinterpret_cast<const long long*>(pair_offsets);
-  const dim3 grid(ts_ceil(max_n, TS_ROWS_PER_BLOCK), S);
+  const dim3 grid(ceil_div(max_n, TS_ROWS_PER_BLOCK), S);
   MCL_CLEAR_ERROR();
   if (want_kl)
     hipLaunchKernelGGL(ts_pair_kernel<true>, grid, dim3(TS_THREADS), 0, st, P, poff, Y, off, max_n, (long long)pairs,

@@ -30,8 +30,6 @@ constexpr int UM_MAX_DRAWS = 4096;              // never met on a valid schedule
 constexpr int UM_THREADS = 256;
 constexpr int UM_WAVES = UM_THREADS / 64;
 
-inline int um_ceil(long long a, long long b) { return (int)((a + b - 1) / b); }
-
 struct um_work {
   double* eps;        // nnz: epochs per attraction of the entry, wmax / w
   double* epn;        // nnz: epochs per negative sample, eps / R
@@ -49,35 +47,6 @@ __host__ __device__ inline um_work um_carve(void* work, long long nnz, int S) {
   w.wmax = w.nneg + nnz;
   w.live = reinterpret_cast<unsigned char*>(w.wmax + S);
   return w;
-}
-
-// the rows of segment s; false (for the whole workgroup) where the offsets do not fit what the launch was sized by
-__device__ __forceinline__ bool um_segment(const long long* off, int s, int max_n, long long rows, long long* o, int* n) {
-  const long long lo = off[s], len = off[s + 1] - lo;
-  if (lo < 0 || len < 2 || len > max_n || lo + len > rows) return false;
-  *o = lo;
-  *n = (int)len;
-  return true;
-}
-
-// the stored entries of segment s: false where nnz_offsets does not fit nnz_total
-__device__ __forceinline__ bool um_entries(const long long* nnz_off, int s, long long nnz_total, long long* base,
-                                           long long* count) {
-  const long long lo = nnz_off[s], len = nnz_off[s + 1] - lo;
-  if (lo < 0 || len < 0 || lo + len > nnz_total) return false;
-  *base = lo;
-  *count = len;
-  return true;
-}
-
-__device__ __forceinline__ bool um_valid_weight(double w) { return w > 0.0 && w <= DBL_MAX; }
-
-// the splitmix64 step
-__host__ __device__ __forceinline__ u64 um_mix(u64 x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
 }
 
 // ---- the schedule: every value one IEEE fp64 operation, no contraction (the restatement's bits)
@@ -115,12 +84,6 @@ __device__ __forceinline__ double um_step(double y, double alpha, double sum) {
 
 __device__ __forceinline__ double um_clip(double v) { return fmin(fmax(v, -4.0), 4.0); }
 
-__device__ __forceinline__ int um_wave_sum_int(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // ----------------------------------------------------------------------------------------------------------- prepare
 __global__ __launch_bounds__(UM_THREADS) void um_wmax_kernel(const double* __restrict__ data,
                                                              const long long* __restrict__ nnz_off, long long nnz_total,
@@ -129,13 +92,13 @@ __global__ __launch_bounds__(UM_THREADS) void um_wmax_kernel(const double* __res
   const int s = blockIdx.x;
   long long base, count;
   double m = 0.0;
-  if (um_entries(nnz_off, s, nnz_total, &base, &count))
+  if (segment_entries(nnz_off, s, nnz_total, &base, &count))
     for (long long e = threadIdx.x; e < count; e += UM_THREADS) {
       const double v = data[base + e];
-      if (um_valid_weight(v)) m = fmax(m, v);
+      if (valid_weight(v)) m = fmax(m, v);
     }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
+  for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));   // wave_max(m) written out: a call changes this kernel's code
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -150,7 +113,7 @@ __global__ __launch_bounds__(UM_THREADS) void um_schedule_kernel(const double* _
                                                                  const int* __restrict__ n_epochs, int rate, um_work w) {
   const int s = blockIdx.y;
   long long base, count;
-  if (!um_entries(nnz_off, s, nnz_total, &base, &count)) return;
+  if (!segment_entries(nnz_off, s, nnz_total, &base, &count)) return;
   const int n_ep = n_epochs[s];
   const bool runs = n_ep >= 1 && n_ep <= UM_MAX_EPOCHS;
   const double wmax = w.wmax[s];
@@ -158,7 +121,7 @@ __global__ __launch_bounds__(UM_THREADS) void um_schedule_kernel(const double* _
     const double v = data[base + e];
     bool live = false;
     double eps = 0.0, epn = 0.0;
-    if (runs && um_valid_weight(v)) um_schedule(v, wmax, n_ep, rate, &live, &eps, &epn);
+    if (runs && valid_weight(v)) um_schedule(v, wmax, n_ep, rate, &live, &eps, &epn);
     w.live[base + e] = live ? 1 : 0;
     w.eps[base + e] = eps;
     w.epn[base + e] = epn;
@@ -177,14 +140,14 @@ __global__ __launch_bounds__(UM_THREADS) void um_init_pca_kernel(const T* __rest
   __shared__ double red[UM_WAVES];
   long long o;
   int n;
-  if (!um_segment(off, blockIdx.x, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.x, 2, max_n, rows, &o, &n)) return;
   double m = 0.0;
   for (int i = threadIdx.x; i < n; i += UM_THREADS) {
     const T* r = x + (o + i) * ld;
     m = fmax(m, fmax(fabs((double)r[0]), fabs((double)r[1])));
   }
 #pragma unroll
-  for (int sh = 32; sh > 0; sh >>= 1) m = fmax(m, __shfl_xor(m, sh, 64));
+  for (int sh = 32; sh > 0; sh >>= 1) m = fmax(m, __shfl_xor(m, sh, 64));   // wave_max(m) written out, as in um_wmax_kernel
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = m;
   __syncthreads();
   m = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
@@ -202,13 +165,13 @@ __global__ __launch_bounds__(UM_THREADS) void um_init_random_kernel(const long l
 #pragma clang fp contract(off)
   long long o;
   int n;
-  if (!um_segment(off, blockIdx.y, max_n, rows, &o, &n)) return;
+  if (!segment_span(off, blockIdx.y, 2, max_n, rows, &o, &n)) return;
   const int i = blockIdx.x * UM_THREADS + threadIdx.x;
   if (i >= n) return;
-  const u64 hi = um_mix(seed0 ^ (u64)i);
+  const u64 hi = mix64(seed0 ^ (u64)i);
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    const u64 h = um_mix(hi ^ (u64)c);
+    const u64 h = mix64(hi ^ (u64)c);
     const double u = (double)(h >> 11) * 0x1p-53;
     const double t = 20.0 * u;
     Y[2 * (o + i) + c] = t - 10.0;
@@ -235,14 +198,14 @@ __global__ __launch_bounds__(UM_THREADS) void um_epoch_kernel(um_args A, int epo
   const int s = blockIdx.y;
   long long o;
   int n;
-  if (!um_segment(A.off, s, A.max_n, A.rows, &o, &n)) return;
+  if (!segment_span(A.off, s, 2, A.max_n, A.rows, &o, &n)) return;
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * UM_WAVES + (threadIdx.x >> 6);
   if (i >= n) return;                                   // a whole wave
   const double2 yi = Ysrc[o + i];
   const int n_ep = A.n_epochs[s];
   long long base = 0, cap = 0, lo = 0, hi = 0;
-  bool ok = n_ep >= 1 && n_ep <= UM_MAX_EPOCHS && epoch < n_ep && um_entries(A.nnz_off, s, A.nnz_total, &base, &cap);
+  bool ok = n_ep >= 1 && n_ep <= UM_MAX_EPOCHS && epoch < n_ep && segment_entries(A.nnz_off, s, A.nnz_total, &base, &cap);
   if (ok) {
     lo = A.indptr[o + s + i];
     hi = A.indptr[o + s + i + 1];
@@ -252,7 +215,7 @@ __global__ __launch_bounds__(UM_THREADS) void um_epoch_kernel(um_args A, int epo
     if (lane == 0) Ydst[o + i] = yi;
     return;
   }
-  const u64 hrow = um_mix(um_mix(A.seed0 ^ (u64)epoch) ^ (u64)i);
+  const u64 hrow = mix64(mix64(A.seed0 ^ (u64)epoch) ^ (u64)i);
   const double nf = (double)epoch;
   const double a = A.a, b = A.b;
   const double att = -2.0 * a * b, rep = 2.0 * A.gamma * b;
@@ -283,9 +246,9 @@ __global__ __launch_bounds__(UM_THREADS) void um_epoch_kernel(um_args A, int epo
       nneg = A.w.nneg[e];
       q = um_draws(nf, nneg, epn);
     }
-    const u64 hent = um_mix(hrow ^ (u64)(r - lo));         // the entry's rank in its row
+    const u64 hent = mix64(hrow ^ (u64)(r - lo));         // the entry's rank in its row
     for (int p = 0; p < q; ++p) {
-      const u64 h = um_mix(hent ^ (u64)p);
+      const u64 h = mix64(hent ^ (u64)p);
       const int k = (int)(((h >> 32) * (u64)n) >> 32);   // < n
       const double2 yk = Ysrc[o + k];
       const double d0 = yi.x - yk.x, d1 = yi.y - yk.y;
@@ -304,8 +267,8 @@ __global__ __launch_bounds__(UM_THREADS) void um_epoch_kernel(um_args A, int epo
   }
   s0 = wave_sum(s0);
   s1 = wave_sum(s1);
-  taken = um_wave_sum_int(taken);
-  drawn = um_wave_sum_int(drawn);
+  taken = wave_sum(taken);
+  drawn = wave_sum(drawn);
   if (lane == 0) {
     const double alpha = um_alpha(A.alpha, epoch, n_ep);
     double2 y;
@@ -350,7 +313,7 @@ int mcl_umap_prepare(const double* data, const int64_t* nnz_offsets, const int32
   MCL_CLEAR_ERROR();
   hipLaunchKernelGGL(um_wmax_kernel, dim3(S), dim3(UM_THREADS), 0, st, data, noff, (long long)nnz_total, w,
                      reinterpret_cast<long long*>(counters));
-  const int blocks = max_nnz > 0 ? (um_ceil(max_nnz, UM_THREADS) < 4096 ? um_ceil(max_nnz, UM_THREADS) : 4096) : 1;
+  const int blocks = max_nnz > 0 ? (ceil_div(max_nnz, UM_THREADS) < 4096 ? ceil_div(max_nnz, UM_THREADS) : 4096) : 1;
   hipLaunchKernelGGL(um_schedule_kernel, dim3(blocks, S), dim3(UM_THREADS), 0, st, data, noff, (long long)nnz_total,
                      n_epochs, negative_sample_rate, w);
   MCL_CHECK_LAUNCH();
@@ -367,8 +330,8 @@ int mcl_umap_init(int32_t mode, const void* x, int64_t ld, int32_t dtype, int32_
   const long long* off = reinterpret_cast<const long long*>(offsets);
   MCL_CLEAR_ERROR();
   if (mode == 1)
-    hipLaunchKernelGGL(um_init_random_kernel, dim3(um_ceil(max_n, UM_THREADS), S), dim3(UM_THREADS), 0, st, off, max_n,
-                       (long long)rows, um_mix((u64)seed ^ ~0ull), Y);
+    hipLaunchKernelGGL(um_init_random_kernel, dim3(ceil_div(max_n, UM_THREADS), S), dim3(UM_THREADS), 0, st, off, max_n,
+                       (long long)rows, mix64((u64)seed ^ ~0ull), Y);
   else if (dtype == 0)
     hipLaunchKernelGGL(um_init_pca_kernel<float>, dim3(S), dim3(UM_THREADS), 0, st, (const float*)x, (long long)ld, off,
                        max_n, (long long)rows, Y);
@@ -408,11 +371,11 @@ int mcl_umap_epochs(int32_t first, int32_t count, const int64_t* indptr, const i
   A.b = b;
   A.gamma = gamma;
   A.alpha = alpha;
-  A.seed0 = um_mix((u64)seed);
+  A.seed0 = mix64((u64)seed);
   A.max_n = max_n;
   A.rate = negative_sample_rate;
   MCL_CLEAR_ERROR();
-  const dim3 grid(um_ceil(max_n, UM_WAVES), S);
+  const dim3 grid(ceil_div(max_n, UM_WAVES), S);
   for (int n = first; n < first + count; ++n) {         // epoch n reads the buffer of its parity and writes the other
     const double2* src = reinterpret_cast<const double2*>(n & 1 ? Y1 : Y0);
     double2* dst = reinterpret_cast<double2*>(n & 1 ? Y0 : Y1);

@@ -157,10 +157,10 @@ def hmrf(z: ArrayLike, graph: Dict[str, object], k: Union[int, Sequence[int]], b
     labels.  ``check=True`` raises ``ValueError`` naming the slide for an ill-defined empirical covariance (status 1) and
     for a neighbour index outside the slide (status bit 4); ``check=False`` returns ``status`` instead."""
     rows, D = _check_scores(z)
-    code = mixture._check_type(covariance_type)
+    code = mixture.check_type(covariance_type)
     off = _offsets(graph, rows)
     seg = np.diff(off)
-    ks = cluster._k_per_segment(k, seg)
+    ks = cluster.k_per_segment(k, seg)
     S, k_max = ks.size, int(ks.max())
     bs = _betas(beta, S)
     if not (tol >= 0.0) or int(max_iter) < 1 or not (reg_covar >= 0.0):
@@ -173,18 +173,18 @@ def hmrf(z: ArrayLike, graph: Dict[str, object], k: Union[int, Sequence[int]], b
         if len(shape) not in (1, 2) or shape[-1] != rows:
             raise ValueError(f"init_labels: expected (R, {rows}) or ({rows},) labels, got shape {shape}")
     dev = device("hmrf")
-    zd = mixture._scores_matrix(z, dev)
+    zd = mixture.scores_matrix(z, dev)
     nbr, w = _graph(graph, dev)
     if init_labels is None:
         init = cluster.kmeans(zd, ks, off, n_init=int(n_init), seed=seed)["labels_all"]
     else:
-        init = mixture._init_labels(init_labels, rows, ks, off, dev)
+        init = mixture.start_labels(init_labels, rows, ks, off, dev)
     R = int(init.shape[0])
     if R > 65535:
         raise ValueError(f"the number of starts must lie in 1 .. 65535, got {R}")
     off_d, ks_d, beta_d = upload(off, dev), upload(ks, dev), upload(bs, dev)
     e = empty(dev)
-    cshape = mixture._cov_shape(covariance_type, k_max, D)
+    cshape = mixture.cov_shape(covariance_type, k_max, D)
     wb = call("mcl_hmrf_workspace_bytes", rows, S, R, D, k_max)
     gb = call("mcl_gmm_workspace_bytes", rows, S, R, D, k_max)
     work = e((wb // 8,), torch.float64)
@@ -235,7 +235,7 @@ def estep(z: ArrayLike, model: Dict[str, object], graph: Dict[str, object], resp
     (rows,) = za, ``score`` (S,) = the mean of lse - za per slide and ``status`` (S,)."""
     rows, D = _check_scores(z)
     ctype = model["covariance_type"]
-    code = mixture._check_type(ctype)
+    code = mixture.check_type(ctype)
     off = _offsets(graph, rows)
     ks = np.asarray(model["k"], dtype=np.int32).reshape(-1)
     S = off.size - 1
@@ -244,7 +244,7 @@ def estep(z: ArrayLike, model: Dict[str, object], graph: Dict[str, object], resp
     if ks.size != S or wts.dim() != 2 or wts.shape[0] != S:
         raise ValueError(f"the model holds {ks.size} slides, the graph has {S}")
     k_max = int(wts.shape[1])
-    if tuple(mu.shape) != (S, k_max, D) or tuple(pc.shape) != (S,) + mixture._cov_shape(ctype, k_max, D):
+    if tuple(mu.shape) != (S, k_max, D) or tuple(pc.shape) != (S,) + mixture.cov_shape(ctype, k_max, D):
         raise ValueError(f"the model's parameters do not match z: means {tuple(mu.shape)}, precisions_cholesky "
                          f"{tuple(pc.shape)}, D = {D}")
     for name, t in (("weights", wts), ("means", mu), ("precisions_cholesky", pc)):
@@ -254,7 +254,7 @@ def estep(z: ArrayLike, model: Dict[str, object], graph: Dict[str, object], resp
         raise ValueError(f"resp_prev: expected shape ({rows}, {k_max}), got {tuple(np.shape(resp_prev))}")
     kw = _check_graph(graph, rows)
     dev = device("hmrf")
-    zd = mixture._scores_matrix(z, dev)
+    zd = mixture.scores_matrix(z, dev)
     q = matrix(resp_prev, "resp_prev", dev, (torch.float64,), torch.float64, dense=True)
     nbr, w = _graph(graph, dev)
     e = empty(dev)
@@ -326,22 +326,22 @@ def scan_beta(z: ArrayLike, graph: Dict[str, object], k: Union[int, Sequence[int
         raise ValueError("betas: expected at least one candidate")
     _betas(np.asarray(cand), len(cand))
     rows, _ = _check_scores(z)
-    mixture._check_type(covariance_type)
+    mixture.check_type(covariance_type)
     off = _offsets(graph, rows, min_rows=2)
     S, B = off.size - 1, len(cand)
-    ks = cluster._k_per_segment(k, np.diff(off))
+    ks = cluster.k_per_segment(k, np.diff(off))
     if S * B > 65535:
         raise ValueError(f"{S} slides x {B} candidates exceed 65535 problems per call")
     _check_graph(graph, rows)
     if init_labels is None and int(n_init) < 1:
         raise ValueError(f"n_init must be >= 1, got {n_init}")
     dev = device("hmrf")
-    zd = mixture._scores_matrix(z, dev)
+    zd = mixture.scores_matrix(z, dev)
     nbr, w = _graph(graph, dev)
     if init_labels is None:
         init = cluster.kmeans(zd, ks, off, n_init=int(n_init), seed=seed)["labels_all"]
     else:
-        init = mixture._init_labels(init_labels, rows, ks, off, dev)
+        init = mixture.start_labels(init_labels, rows, ks, off, dev)
     big = {"nbr": nbr.repeat(B, 1), "w": w.repeat(B, 1),
            "offsets": np.concatenate([[0]] + [off[1:] + g * rows for g in range(B)]).astype(np.int64)}
     zz = zd.contiguous().repeat(B, 1)

@@ -38,9 +38,8 @@ import numpy as np
 import torch
 
 from . import _arrays, neighbors, umap
-from ._arrays import ArrayLike, Tensor, dense, device, empty, upload
+from ._arrays import ArrayLike, Tensor, check_int, dense, device, empty, upload
 from ._lib import call
-from .umap import _check_graph
 
 MAX_ROWS = 16384         # csrc/leiden.hip
 MAX_SEGMENTS = 65535
@@ -56,12 +55,6 @@ _KEYWORDS = ("resolution", "n_iterations", "partition", "max_levels", "max_sweep
 
 
 # ------------------------------------------------------------------------------------------------------- host rules
-def _check_int(name: str, v, lo: int) -> int:
-    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo:
-        raise ValueError(f"{name} must be an integer >= {lo}, got {v!r}")
-    return int(v)
-
-
 def _check_params(resolution, n_iterations=-1, max_levels=MAX_LEVELS, max_sweeps=MAX_SWEEPS) -> None:
     if isinstance(resolution, bool) or not isinstance(resolution, (int, float, np.integer, np.floating)):
         raise ValueError(f"resolution must be a number, got {resolution!r}")
@@ -69,8 +62,8 @@ def _check_params(resolution, n_iterations=-1, max_levels=MAX_LEVELS, max_sweeps
         raise ValueError(f"resolution must be finite and positive, got {resolution!r}")
     if isinstance(n_iterations, bool) or not isinstance(n_iterations, (int, np.integer)) or n_iterations == 0 or n_iterations < -1:
         raise ValueError(f"n_iterations must be -1 (until nothing changes) or a positive integer, got {n_iterations!r}")
-    _check_int("max_levels", max_levels, 1)
-    _check_int("max_sweeps", max_sweeps, 1)
+    check_int(max_levels, "max_levels", 1)
+    check_int(max_sweeps, "max_sweeps", 1)
 
 
 def _check_keywords(kw: Dict[str, object]) -> None:
@@ -110,7 +103,7 @@ class _Run:
     """The device side of one call: the graph's tensors, the workspace and the launches."""
 
     def __init__(self, graph: Dict[str, object], resolution: float, max_levels: int = MAX_LEVELS, max_sweeps: int = MAX_SWEEPS):
-        off, nnz_off = _check_graph(graph)
+        off, nnz_off = umap.check_graph(graph)
         self.off, self.seg = off, np.diff(off)
         self.S, self.rows, self.total = int(self.seg.size), int(off[-1]), int(nnz_off[-1])
         self.max_n, self.gamma = int(self.seg.max()), float(resolution)
@@ -197,7 +190,7 @@ def leiden(graph: Dict[str, object], resolution: float = 1.0, n_iterations: int 
     alone).  Returns ``labels`` (rows,) int32 on the device and, per slide on the host, ``n_clusters``, ``modularity``
     (fp64), ``levels``, ``sweeps``, ``accepted_sweeps``, ``rounds``, ``iterations`` and ``offsets``."""
     _check_params(resolution, n_iterations, max_levels, max_sweeps)
-    off, _ = _check_graph(graph)
+    off, _ = umap.check_graph(graph)
     rows = int(off[-1])
     start = None
     if partition is not None:
@@ -232,7 +225,7 @@ def leiden(graph: Dict[str, object], resolution: float = 1.0, n_iterations: int 
 def modularity(graph: Dict[str, object], labels: ArrayLike, resolution: float = 1.0) -> np.ndarray:
     """Q of ``labels`` ((rows,) integer ids, host or device) per slide, computed by the kernels of ``leiden``: (S,) fp64."""
     _check_params(resolution)
-    off, _ = _check_graph(graph)
+    off, _ = umap.check_graph(graph)
     _check_labels(labels, int(off[-1]), "labels")
     start = canonical(labels, off)
     run = _Run(graph, resolution)
@@ -243,7 +236,7 @@ def refine(graph: Dict[str, object], partition: ArrayLike, resolution: float = 1
     """The refinement of ``partition`` at level 0: (rows,) int32 on the device, every vertex labelled by the smallest row (within
     its slide) of its refined community.  Each refined community lies inside one community of ``partition`` and is connected."""
     _check_params(resolution)
-    off, _ = _check_graph(graph)
+    off, _ = umap.check_graph(graph)
     _check_labels(partition, int(off[-1]), "partition")
     start = canonical(partition, off)
     run = _Run(graph, resolution)
@@ -277,7 +270,7 @@ def expression_clusters(expr: ArrayLike, batch_idx=None, preprocess: bool = True
     if layout:
         if n_pcs < 2:
             raise ValueError(f"n_pcs must be at least 2 for the PCA start of the layout, got {n_pcs}")
-        umap._check_keywords(umap_kw.get("init", "pca"), {k: v for k, v in umap_kw.items() if k != "init"})
+        umap.check_keywords(umap_kw.get("init", "pca"), {k: v for k, v in umap_kw.items() if k != "init"})
     graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors,
                                        pca_solver)
     embedding = None

@@ -47,8 +47,8 @@ import numpy as np
 import torch
 
 from . import markers, spatial
-from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, nanmean,
-                      stack_rows, upload)
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, check_flag, check_int, cumulative_offsets, device, empty,
+                      load_gene_major, matrix, nanmean, stack_rows, upload)
 from ._lib import call
 
 MAX_ROWS = 16384         # csrc/ligrec.hip: the uint16 permutation tables of csrc/spatial.hip
@@ -111,14 +111,14 @@ def prepare_interactions(interactions, G: int, complex_policy: str = "min"):
 
 
 def check_options(n_perms, seed, threshold, corr_axis, return_permutations=False):
-    P = spatial._check_int(n_perms, "n_perms", 0, MAX_PERMS)
-    seed = spatial._check_int(seed, "seed", 0, 2 ** 64 - 1)
+    P = check_int(n_perms, "n_perms", 0, MAX_PERMS)
+    seed = check_int(seed, "seed", 0, 2 ** 64 - 1)
     if isinstance(threshold, (bool, np.bool_)) or not isinstance(threshold, (int, float, np.integer, np.floating)) or \
             not 0.0 <= float(threshold) <= 1.0:
         raise ValueError(f"threshold must be a number in 0 .. 1, got {threshold!r}")
     if corr_axis not in CORR_AXES:
         raise ValueError(f"corr_axis must be one of {list(CORR_AXES)}, got {corr_axis!r}")
-    spatial._check_flag(return_permutations, "return_permutations")
+    check_flag(return_permutations, "return_permutations")
     return P, seed, float(threshold)
 
 
@@ -189,7 +189,7 @@ def ligrec_device(x: ArrayLike, labels, interactions, offsets: Optional[Sequence
         P = len(permutations[0])
     dev = device("ligrec")
     xd = matrix(x, "x", dev, FLOAT_CODE, lambda t: torch.float32 if t.dtype == torch.float16 else torch.float64)
-    lab_d = markers._labels(labels, rows, dev)
+    lab_d = markers.device_labels(labels, rows, dev)
     S, max_n, kmax, U, I = int(sizes.size), int(sizes.max()), int(kk.max()), int(used.size), len(sides)
     mask = _ALL_COLUMNS
     if host_labels:

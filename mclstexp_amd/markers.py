@@ -37,8 +37,8 @@ import numpy as np
 import torch
 
 from . import cluster
-from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, device, empty, load_gene_major, matrix, stack_rows,
-                      upload, validate_offsets)
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, check_flag, cumulative_offsets, device, empty, load_gene_major, matrix,
+                      stack_rows, upload, validate_offsets)
 from ._lib import call
 
 MAX_ROWS = 16384         # csrc/markers.hip: a column's keys and group bytes sit in LDS
@@ -56,9 +56,8 @@ FULL = ("means", "vars", "means_rest", "vars_rest", "pts", "pts_rest")
 def _check_options(method, tie_correct, n_genes, rankby_abs, G: int) -> int:
     if method not in METHODS:
         raise ValueError(f"method must be one of {sorted(METHODS)}, got {method!r}")
-    for name, v in (("tie_correct", tie_correct), ("rankby_abs", rankby_abs)):
-        if not isinstance(v, (bool, np.bool_)):
-            raise ValueError(f"{name} must be a bool, got {v!r}")
+    check_flag(tie_correct, "tie_correct")
+    check_flag(rankby_abs, "rankby_abs")
     if n_genes is None:
         return G
     if isinstance(n_genes, bool) or not isinstance(n_genes, (int, np.integer)) or n_genes < 1:
@@ -66,7 +65,8 @@ def _check_options(method, tie_correct, n_genes, rankby_abs, G: int) -> int:
     return min(int(n_genes), G)
 
 
-def _check_k(k, S: int) -> np.ndarray:
+def check_k(k, S: int) -> np.ndarray:
+    """``k`` as int32 per slide: an int stands for every slide; each 1 .. MAX_GROUPS."""
     kk = np.asarray(k)
     if kk.ndim == 0:
         kk = np.full(S, kk)
@@ -77,7 +77,8 @@ def _check_k(k, S: int) -> np.ndarray:
     return kk.astype(np.int32)
 
 
-def _labels(labels, rows: int, dev: torch.device) -> Tensor:
+def device_labels(labels, rows: int, dev: torch.device) -> Tensor:
+    """The group ids of ``rows`` spots as an int32 device tensor; a tensor must already be int32."""
     if isinstance(labels, Tensor):
         if labels.dtype != torch.int32 or tuple(labels.shape) != (rows,):
             raise ValueError(f"labels: a tensor must be int32 of shape ({rows},), got {labels.dtype} {tuple(labels.shape)}")
@@ -114,7 +115,7 @@ def check_problem(shape: Sequence[int], offsets, k, labels=None):
         if lab.shape != (rows,) or not np.issubdtype(lab.dtype, np.integer):
             raise ValueError(f"labels: expected {rows} integer group ids, got shape {lab.shape} dtype {lab.dtype}")
         k = infer_k(lab, off)
-    return off, _check_k(k, off.size - 1)
+    return off, check_k(k, off.size - 1)
 
 
 # ----------------------------------------------------------------------------------------------------------- device
@@ -134,7 +135,7 @@ def rank_genes_groups_device(x: ArrayLike, labels, offsets: Optional[Sequence[in
     n_top = _check_options(method, tie_correct, n_genes, rankby_abs, G)
     dev = device("markers")
     xd = matrix(x, "x", dev, FLOAT_CODE, lambda t: torch.float32 if t.dtype == torch.float16 else torch.float64)
-    lab_d = _labels(labels, rows, dev)
+    lab_d = device_labels(labels, rows, dev)
     S, max_n, kmax = int(kk.size), int(np.diff(off).max()), int(kk.max())
     goff = cumulative_offsets(kk)
     KT = int(goff[-1])

@@ -47,11 +47,13 @@ _PER_SLIDE = ("weights", "means", "covariances", "precisions_cholesky", "lower_b
               "bic", "aic", "restart")
 
 
-def _cov_shape(ctype: str, k_max: int, D: int) -> tuple:
+def cov_shape(ctype: str, k_max: int, D: int) -> tuple:
+    """The shape of one slide's covariances (and precisions_cholesky) of type ``ctype``."""
     return {"full": (k_max, D, D), "tied": (D, D), "diag": (k_max, D), "spherical": (k_max,)}[ctype]
 
 
-def _scores_matrix(z: ArrayLike, dev: torch.device) -> Tensor:
+def scores_matrix(z: ArrayLike, dev: torch.device) -> Tensor:
+    """``z`` as a float64 row-major device matrix of 1 .. MAX_DIM columns."""
     if not isinstance(z, Tensor) and np.asarray(z).ndim != 2:
         raise ValueError(f"z: expected a 2-D (rows, D) array, got shape {np.asarray(z).shape}")
     D = int(z.shape[1])
@@ -63,13 +65,15 @@ def _scores_matrix(z: ArrayLike, dev: torch.device) -> Tensor:
     return zd
 
 
-def _check_type(covariance_type: str) -> int:
+def check_type(covariance_type: str) -> int:
+    """The C ABI's code of ``covariance_type``."""
     if covariance_type not in COVARIANCE_TYPES:
         raise ValueError(f"covariance_type must be one of {sorted(COVARIANCE_TYPES)}, got {covariance_type!r}")
     return COVARIANCE_TYPES[covariance_type]
 
 
-def _init_labels(init_labels, rows: int, ks: np.ndarray, off: np.ndarray, dev: torch.device) -> Tensor:
+def start_labels(init_labels, rows: int, ks: np.ndarray, off: np.ndarray, dev: torch.device) -> Tensor:
+    """Start labels as an int32 (R, rows) device tensor; host labels are checked against 0 .. k - 1 of their slide."""
     t = init_labels if isinstance(init_labels, Tensor) else torch.as_tensor(np.asarray(init_labels))
     if t.dim() == 1:
         t = t[None, :]
@@ -100,12 +104,12 @@ def gmm(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequence[i
     ``weights_all`` ... ``status_all`` (S, R, ...), ``score_all`` (S, R): the mean log-likelihood under the final
     parameters; ``init_labels`` (R, rows) as used; host ``k`` (S,), ``offsets`` and ``covariance_type``."""
     dev = device("mixture")
-    zd = _scores_matrix(z, dev)
+    zd = scores_matrix(z, dev)
     rows, D = int(zd.shape[0]), int(zd.shape[1])
-    code = _check_type(covariance_type)
+    code = check_type(covariance_type)
     off = cluster.validate_offsets(offsets, rows)
     seg = np.diff(off)
-    ks = cluster._k_per_segment(k, seg)
+    ks = cluster.k_per_segment(k, seg)
     S, k_max = ks.size, int(ks.max())
     if not (tol >= 0.0) or int(max_iter) < 1 or not (reg_covar >= 0.0):
         raise ValueError(f"tol and reg_covar must be >= 0 and max_iter >= 1, got {tol}, {reg_covar}, {max_iter}")
@@ -114,13 +118,13 @@ def gmm(z: ArrayLike, k: Union[int, Sequence[int]], offsets: Optional[Sequence[i
             raise ValueError(f"n_init must be >= 1, got {n_init}")
         init = cluster.kmeans(zd, ks, off, n_init=int(n_init), seed=seed)["labels_all"]
     else:
-        init = _init_labels(init_labels, rows, ks, off, dev)
+        init = start_labels(init_labels, rows, ks, off, dev)
     R = int(init.shape[0])
     if R > 65535:
         raise ValueError(f"the number of starts must lie in 1 .. 65535, got {R}")
     off_d, ks_d = upload(off, dev), upload(ks, dev)
     e = empty(dev)
-    cshape = _cov_shape(covariance_type, k_max, D)
+    cshape = cov_shape(covariance_type, k_max, D)
     wb = call("mcl_gmm_workspace_bytes", rows, S, R, D, k_max)
     work = e((wb // 8,), torch.float64)
     f64, i32 = torch.float64, torch.int32
@@ -157,10 +161,10 @@ def predict(z: ArrayLike, model: Dict[str, object], offsets: Optional[Sequence[i
     ``log_resp`` (rows, k_max), ``log_prob_norm`` (rows,) = sklearn's ``score_samples``, ``score`` (S,) its mean per slide.
     ``offsets``: the segments of ``z`` (one per slide of the model; None: one segment)."""
     dev = device("mixture")
-    zd = _scores_matrix(z, dev)
+    zd = scores_matrix(z, dev)
     rows, D = int(zd.shape[0]), int(zd.shape[1])
     ctype = model["covariance_type"]
-    code = _check_type(ctype)
+    code = check_type(ctype)
     off = cluster.validate_offsets(offsets, rows)
     ks = np.asarray(model["k"], dtype=np.int32).reshape(-1)
     S = off.size - 1
@@ -168,7 +172,7 @@ def predict(z: ArrayLike, model: Dict[str, object], offsets: Optional[Sequence[i
     if ks.size != S or w.dim() != 2 or w.shape[0] != S:
         raise ValueError(f"the model holds {ks.size} slides, z has {S} segments")
     k_max = int(w.shape[1])
-    if tuple(mu.shape) != (S, k_max, D) or tuple(pc.shape) != (S,) + _cov_shape(ctype, k_max, D):
+    if tuple(mu.shape) != (S, k_max, D) or tuple(pc.shape) != (S,) + cov_shape(ctype, k_max, D):
         raise ValueError(f"the model's parameters do not match z: means {tuple(mu.shape)}, precisions_cholesky "
                          f"{tuple(pc.shape)}, D = {D}")
     for name, t in (("weights", w), ("means", mu), ("precisions_cholesky", pc)):
@@ -190,16 +194,16 @@ def m_step(z: ArrayLike, log_resp: ArrayLike, k: Union[int, Sequence[int]], offs
     ``means``, ``covariances``, ``precisions_cholesky`` (S, ...) and ``status`` (S,), plus ``k`` and ``covariance_type``, so
     that the result is a model ``predict`` takes.  Nothing is raised for an ill-defined covariance: read ``status``."""
     dev = device("mixture")
-    zd = _scores_matrix(z, dev)
+    zd = scores_matrix(z, dev)
     rows, D = int(zd.shape[0]), int(zd.shape[1])
-    code = _check_type(covariance_type)
+    code = check_type(covariance_type)
     off = cluster.validate_offsets(offsets, rows)
-    ks = cluster._k_per_segment(k, np.diff(off))
+    ks = cluster.k_per_segment(k, np.diff(off))
     S, k_max = ks.size, int(ks.max())
     lr = matrix(log_resp, "log_resp", dev, (torch.float64,), torch.float64, dense=True)
     if tuple(lr.shape) != (rows, k_max):
         raise ValueError(f"log_resp: expected shape ({rows}, {k_max}), got {tuple(lr.shape)}")
-    cshape = _cov_shape(covariance_type, k_max, D)
+    cshape = cov_shape(covariance_type, k_max, D)
     z0 = lambda shape: torch.zeros(shape, device=dev, dtype=torch.float64)      # noqa: E731
     res = {"weights": z0((S, k_max)), "means": z0((S, k_max, D)), "covariances": z0((S,) + cshape),
            "precisions_cholesky": z0((S,) + cshape), "status": torch.empty((S,), device=dev, dtype=torch.int32)}
@@ -231,13 +235,13 @@ def select_k(z: ArrayLike, k_range: Sequence[int], offsets: Optional[Sequence[in
     if not cand or len(set(cand)) != len(cand):
         raise ValueError(f"k_range: expected distinct candidates, got {list(k_range)}")
     dev = device("mixture")
-    zd = _scores_matrix(z, dev)
+    zd = scores_matrix(z, dev)
     rows, D = int(zd.shape[0]), int(zd.shape[1])
     off = cluster.validate_offsets(offsets, rows)
     S = off.size - 1
     seg = np.diff(off)
     for c in cand:
-        cluster._k_per_segment(c, seg)
+        cluster.k_per_segment(c, seg)
     if init_labels is not None and set(init_labels) != set(cand):
         raise ValueError(f"init_labels: expected one entry per candidate {cand}, got {sorted(init_labels)}")
     R = int(n_init) if init_labels is None else int(np.atleast_2d(np.asarray(
@@ -298,7 +302,7 @@ def validity(z: ArrayLike, labels: ArrayLike, offsets: Optional[Sequence[int]] =
     (sklearn's, Euclidean; NaN for a row labelled -1) and host ``silhouette``, ``calinski_harabasz``, ``davies_bouldin``
     (S,).  Labels are integers in [0, 1024); -1 drops the row.  2 .. 50 000 rows per segment."""
     dev = device("mixture")
-    zd = _scores_matrix(z, dev)
+    zd = scores_matrix(z, dev)
     rows, D = int(zd.shape[0]), int(zd.shape[1])
     off = cluster.validate_offsets(offsets, rows, min_rows=2)
     t = labels if isinstance(labels, Tensor) else torch.as_tensor(np.asarray(labels))

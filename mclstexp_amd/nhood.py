@@ -44,7 +44,8 @@ import numpy as np
 import torch
 
 from . import markers, spatial
-from ._arrays import ArrayLike, Tensor, cumulative_offsets, device, empty, nanmean, upload, validate_offsets
+from ._arrays import (ArrayLike, Tensor, check_flag, check_int, cumulative_offsets, device, empty, nanmean, upload,
+                      validate_offsets)
 from ._lib import call
 from .ligrec import kept_sizes
 
@@ -90,12 +91,12 @@ def check_labels(labels, rows: int, offsets: np.ndarray, k):
             raise ValueError("k: needed when the labels are a device tensor")
         if labels.dtype != torch.int32 or tuple(labels.shape) != (rows,):
             raise ValueError(f"labels: a tensor must be int32 of shape ({rows},), got {labels.dtype} {tuple(labels.shape)}")
-        return markers._check_k(k, S)
+        return markers.check_k(k, S)
     lab = np.asarray(labels)
     if lab.shape != (rows,) or not np.issubdtype(lab.dtype, np.integer) or lab.dtype == np.bool_:
         raise ValueError(f"labels: expected {rows} integer group ids (-1: not part of the analysis), got shape {lab.shape} "
                          f"dtype {lab.dtype}")
-    kk = markers._check_k(markers.infer_k(lab, offsets) if k is None else k, S)
+    kk = markers.check_k(markers.infer_k(lab, offsets) if k is None else k, S)
     for s in range(S):
         seg = lab[offsets[s]:offsets[s + 1]]
         bad = int(((seg < -1) | (seg >= int(kk[s]))).sum())
@@ -161,7 +162,7 @@ def greedy_match(table) -> np.ndarray:
 
 # ----------------------------------------------------------------------------------------------------------- device
 def _prepare(labels, rows: int, off: np.ndarray, kk: np.ndarray, dev: torch.device) -> Dict[str, object]:
-    lab_d = markers._labels(labels, rows, dev)
+    lab_d = markers.device_labels(labels, rows, dev)
     S, max_n, kmax = int(off.size - 1), int(np.diff(off).max()), int(kk.max())
     e = empty(dev)
     i32 = torch.int32
@@ -192,8 +193,8 @@ def nhood_device(labels, graph: Dict[str, object], k=None, n_perms: int = 1000, 
     ``kept_offsets`` (S + 1,), ``status`` and, with permutations, ``table`` (the uint16 tables as int16); on the host
     ``offsets``, ``k``, ``n_perms``.  The one read-back is the status."""
     off, rows, kw = check_graph(graph)
-    P = spatial._check_int(n_perms, "n_perms", 0, MAX_PERMS)
-    seed = spatial._check_int(seed, "seed", 0, 2 ** 64 - 1)
+    P = check_int(n_perms, "n_perms", 0, MAX_PERMS)
+    seed = check_int(seed, "seed", 0, 2 ** 64 - 1)
     kk = check_labels(labels, rows, off, k)
     S, kmax = int(off.size - 1), int(kk.max())
     check_cells(S, kmax, 1, "nhood")
@@ -265,7 +266,7 @@ def nhood_enrichment(labels, graph: Dict[str, object], k=None, n_perms: int = 10
 
 def interaction_matrix(labels, graph: Dict[str, object], k=None, normalized: bool = False) -> List[np.ndarray]:
     """``count`` of every slide; ``normalized``: every row divided by its sum (NaN where that is 0)."""
-    spatial._check_flag(normalized, "normalized")
+    check_flag(normalized, "normalized")
     res = nhood_enrichment(labels, graph, k, n_perms=0)
     if not normalized:
         return [r["count"] for r in res]
@@ -324,7 +325,7 @@ def co_occurrence(coords: ArrayLike, labels, offsets: Optional[Sequence[int]] = 
             if not np.isfinite(host_c[off[s]:off[s + 1]]).all():
                 raise ValueError(f"coords: slide {s} holds non-finite coordinates")
     if isinstance(radii, (int, np.integer)) and not isinstance(radii, (bool, np.bool_)):
-        T = spatial._check_int(radii, "radii", 1, MAX_RADII)
+        T = check_int(radii, "radii", 1, MAX_RADII)
         check_cells(S, kmax, T, "co_occurrence")
         c = host_c if host_c is not None else dev_c.cpu().numpy().astype(np.float64)
         lab = labels.cpu().numpy() if isinstance(labels, Tensor) else np.asarray(labels)

@@ -39,8 +39,8 @@ import numpy as np
 import torch
 
 from . import neighbors
-from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, cumulative_offsets, dense, device, empty, load_gene_major, matrix,
-                      stack_rows, upload, validate_offsets)
+from ._arrays import (FLOAT_CODE, ArrayLike, Tensor, check_flag, check_int, cumulative_offsets, dense, device, empty,
+                      load_gene_major, matrix, stack_rows, upload, validate_offsets)
 from ._lib import call
 
 MAX_ROWS = 16384         # csrc/spatial.hip: 14 index bits in a permutation key, uint16 tables
@@ -59,26 +59,14 @@ _PER_GENE = ("stat", "z_norm", "pval_norm", "neglog10_pval_norm", "pval_norm_adj
 
 
 # ------------------------------------------------------------------------------------------------------- host rules
-def _check_int(v, name: str, lo: int, hi: int) -> int:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo or v > hi:
-        raise ValueError(f"{name} must be an integer in {lo} .. {hi}, got {v!r}")
-    return int(v)
-
-
-def _check_flag(v, name: str) -> bool:
-    if not isinstance(v, (bool, np.bool_)):
-        raise ValueError(f"{name} must be a bool, got {v!r}")
-    return bool(v)
-
-
 def check_lattice(shape: Sequence[int], offsets, k, prune, row_standardise):
     """The limits of ``lattice``, checked on the host before the GPU is touched.  Returns (offsets int64, k, prune code)."""
     if len(shape) != 2 or int(shape[1]) != 2:
         raise ValueError(f"coords: expected a (rows, 2) array, got shape {tuple(shape)}")
-    k = _check_int(k, "k", 1, MAX_K)
+    k = check_int(k, "k", 1, MAX_K)
     if prune not in PRUNES:
         raise ValueError(f"prune must be one of {sorted(PRUNES)}, got {prune!r}")
-    _check_flag(row_standardise, "row_standardise")
+    check_flag(row_standardise, "row_standardise")
     off = validate_offsets(offsets, int(shape[0]), min_rows=2, max_rows=MAX_ROWS, max_segments=MAX_SLIDES, none_is_one=True,
                            noun="slide")
     seg = np.diff(off)
@@ -99,10 +87,10 @@ def check_autocorr(shape: Sequence[int], graph, mode, n_perms, seed, two_tailed,
         raise ValueError(f"x has {rows} rows, the graph {int(graph['offsets'][-1])}")
     if mode not in MODES:
         raise ValueError(f"mode must be one of {list(MODES)}, got {mode!r}")
-    P = _check_int(n_perms, "n_perms", 0, MAX_PERMS)
-    seed = _check_int(seed, "seed", 0, 2 ** 64 - 1)
-    _check_flag(two_tailed, "two_tailed")
-    _check_flag(return_sims, "return_sims")
+    P = check_int(n_perms, "n_perms", 0, MAX_PERMS)
+    seed = check_int(seed, "seed", 0, 2 ** 64 - 1)
+    check_flag(two_tailed, "two_tailed")
+    check_flag(return_sims, "return_sims")
     return rows, G, P, seed
 
 
@@ -141,7 +129,7 @@ def lattice(coords: Optional[ArrayLike] = None, offsets: Optional[Sequence[int]]
             raise ValueError("a given graph needs both nbr= and w= and no coords")
         if len(nbr.shape) != 2:
             raise ValueError(f"nbr: expected a 2-D (rows, k) array, got shape {tuple(nbr.shape)}")
-        rows, k = int(nbr.shape[0]), _check_int(int(nbr.shape[1]), "k", 1, MAX_K)
+        rows, k = int(nbr.shape[0]), check_int(int(nbr.shape[1]), "k", 1, MAX_K)
         off = validate_offsets(offsets, rows, min_rows=2, max_rows=MAX_ROWS, max_segments=MAX_SLIDES, none_is_one=True,
                                noun="slide")
         code = 0
@@ -265,7 +253,7 @@ def autocorr(x: ArrayLike, graph: Dict[str, object], mode: str = "moran", n_perm
     (P, G) with ``return_sims``).  ``return_permutations`` adds ``permutations`` (P, n) per slide."""
     shape = tuple(x.shape) if hasattr(x, "shape") else np.asarray(x).shape
     check_autocorr(shape, graph, mode, n_perms, seed, two_tailed, return_sims)
-    _check_flag(return_permutations, "return_permutations")
+    check_flag(return_permutations, "return_permutations")
     d = autocorr_device(x, graph, n_perms, seed, permutations, two_tailed)
     P, off = int(d["n_perms"]), graph["offsets"]
     keys = [key for key in _PER_GENE if key in d]

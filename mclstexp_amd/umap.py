@@ -91,9 +91,7 @@ def _check_params(a, b, gamma: float, alpha: float, negative_sample_rate: int, s
     for name, v in (("a", a), ("b", b)):
         if v is not None and not float(v) > 0:
             raise ValueError(f"{name} must be positive, got {v!r}")
-    r = negative_sample_rate
-    if isinstance(r, bool) or not isinstance(r, (int, np.integer)) or not 0 <= r <= MAX_RATE:
-        raise ValueError(f"negative_sample_rate must be an integer in 0 .. {MAX_RATE}, got {r!r}")
+    _arrays.check_int(negative_sample_rate, "negative_sample_rate", 0, MAX_RATE)
     if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
         raise ValueError(f"seed must be an integer (taken modulo 2^64), got {seed!r}")
     if stop_after is not None and (isinstance(stop_after, bool) or not isinstance(stop_after, (int, np.integer))
@@ -101,7 +99,7 @@ def _check_params(a, b, gamma: float, alpha: float, negative_sample_rate: int, s
         raise ValueError(f"stop_after must be None or an integer >= 0, got {stop_after!r}")
 
 
-def _check_keywords(init, kw: Dict[str, object]) -> None:
+def check_keywords(init, kw: Dict[str, object]) -> None:
     """The checks of ``layout``'s keywords that need no graph, for the callers that build the graph first."""
     unknown = set(kw) - {"n_epochs", "a", "b", "min_dist", "spread", "alpha", "gamma", "negative_sample_rate", "seed",
                          "stop_after"}
@@ -113,7 +111,8 @@ def _check_keywords(init, kw: Dict[str, object]) -> None:
     validate_epochs(kw.get("n_epochs"), np.array([2]))
 
 
-def _check_graph(graph: Dict[str, object]) -> Tuple[np.ndarray, np.ndarray]:
+def check_graph(graph: Dict[str, object]) -> Tuple[np.ndarray, np.ndarray]:
+    """(offsets, nnz_offsets) as int64 of a graph dict of ``neighbors``, after checking its keys and array lengths."""
     for key in ("indptr", "indices", "data", "offsets", "nnz_offsets"):
         if key not in graph:
             raise ValueError(f"graph: expected the dict of neighbors.neighbors() or connectivities(); it has no {key!r}")
@@ -176,7 +175,7 @@ def layout(graph: Dict[str, object], init: Union[str, ArrayLike] = "pca", x: Opt
     drawn), ``n_epochs`` ((S,) int32), ``a``, ``b`` and the host ``offsets``."""
     _check_init(init)
     _check_params(a, b, gamma, alpha, negative_sample_rate, seed, stop_after)
-    off, nnz_off = _check_graph(graph)
+    off, nnz_off = check_graph(graph)
     seg = np.diff(off)
     S, rows, total = int(seg.size), int(off[-1]), int(nnz_off[-1])
     epochs = validate_epochs(n_epochs, seg)
@@ -219,7 +218,7 @@ def layout(graph: Dict[str, object], init: Union[str, ArrayLike] = "pca", x: Opt
 def umap(x: ArrayLike, offsets: Optional[Sequence[int]] = None, n_neighbors: int = 15, init: Union[str, ArrayLike] = "pca",
          **kw) -> Dict[str, object]:
     """``neighbors.neighbors(x, offsets, n_neighbors)`` then ``layout`` (its keywords): the layout's dict plus ``graph``."""
-    _check_keywords(init, kw)
+    check_keywords(init, kw)
     graph = neighbors.neighbors(x, offsets, n_neighbors)
     res = layout(graph, init, x=x, **kw)
     res["graph"] = graph
@@ -235,7 +234,7 @@ def expression_umap(expr: ArrayLike, batch_idx=None, preprocess: bool = True, no
     if n_pcs < 2:
         raise ValueError(f"n_pcs must be at least 2 for the PCA start, got {n_pcs}")
     init = kw.pop("init", "pca")
-    _check_keywords(init, kw)
+    check_keywords(init, kw)
     graph = neighbors.expression_graph(expr, batch_idx, preprocess, normalize_and_log, n_top_genes, n_pcs, n_neighbors,
                                        pca_solver)
     res = layout(graph, init, x=graph["scores"], **kw)

@@ -28,7 +28,9 @@ def test_device_header_defines_the_shared_helpers():
     names = defined_names(open(os.path.join(CSRC, "device.h")).read())
     for n in ("bf16_t", "bf16x2_t", "bf16x8", "v4s", "f32x2", "f32x4", "f32x16", "u32x2", "u32x4", "u64", "bf_lo",
               "bf_hi", "bf2f", "pack_bf16", "f2bf", "round_bf16", "pack8", "unpack8", "ldd", "lanes_below", "half_wave_sum",
-              "opaque_lane", "glds16", "glds16s", "glds4", "buffer_lds16", "bn_relu_chunk", "MCL_LDSP", "MCL_GLBP"):
+              "opaque_lane", "glds16", "glds16s", "glds4", "buffer_lds16", "bn_relu_chunk", "MCL_LDSP", "MCL_GLBP", "wave_sum",
+              "wave_max", "wave_min", "block_sum4", "order_key", "key_value", "mix64", "segment_rows", "segment_span",
+              "segment_entries", "valid_weight", "clamp_index"):
         assert n in names, n
     assert '#include "device.h"' in open(os.path.join(CSRC, "common.h")).read()
 
@@ -39,3 +41,33 @@ def test_no_kernel_file_redefines_a_device_header_name():
     assert len(srcs) > 20
     copies = {os.path.basename(p): sorted(defined_names(open(p).read()) & shared) for p in srcs}
     assert not {k: v for k, v in copies.items() if v}, "defined in csrc/device.h, use it from there"
+
+
+# a helper that differs from device.h's keeps a name of its own; (file, name): the difference, stated at the definition too
+LOCAL_FORMS = {
+    ("spatial.hip", "sp_slide_rows"): "tests r1 < r0 ahead of the subtraction, terms in another order: segment_rows changes "
+                                      "the code of the file's kernels",
+}
+COPY_NAMES = re.compile(r"\w+_wave_(sum|total|count|max|min)\w*|wave_(min|max)_f64|\w+_slide_rows|\w+_(mix|mix64)|"
+                        r"\w+_valid_weight|\w+_ceil")
+
+
+def defined_functions(text):
+    """Names of the functions, host or device, that a C++ source defines at file scope."""
+    return set(re.findall(r"^[A-Za-z_][^;{}()=#\n]*?[\s*&](\w+)\s*\(", _strip(text), flags=re.M))
+
+
+def test_no_kernel_file_keeps_a_copy_of_a_lane_segment_or_hash_helper():
+    srcs = sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    found = {}
+    for p in srcs:
+        name, text = os.path.basename(p), open(p).read()
+        assert "9e3779b97f4a7c15" not in text.lower(), f"{name}: the splitmix64 step is device.h's mix64"
+        for fn in defined_functions(text):
+            if COPY_NAMES.fullmatch(fn):
+                found[(name, fn)] = text
+    assert set(found) == set(LOCAL_FORMS), "a copy of a csrc/device.h helper (or an entry of LOCAL_FORMS that is gone)"
+    for (name, fn), text in found.items():      # the reason stands at the definition: a comment right above it
+        lines = text.splitlines()
+        at = next(i for i, l in enumerate(lines) if re.match(r"[A-Za-z_].*\b%s\s*\(" % fn, l))
+        assert lines[at - 1].startswith("//") and "device.h" in "".join(lines[max(0, at - 3):at]), (name, fn)
