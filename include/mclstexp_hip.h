@@ -1481,6 +1481,40 @@ int mcl_cooccur_counts(const double* coords, const int64_t* offsets, const int32
                        int32_t T, void* work, int32_t* pairs, int32_t* status, mcl_stream_t stream);
 int mcl_cooccur_scores(const int32_t* k, int32_t S, int32_t kmax, int32_t T, int32_t* pairs, double* occ, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- spots as mixtures of signatures (ABI 13, entry points
+ * added; csrc/deconv.hip).  b_i = argmin over b >= 0 of || x_i - S^T b ||_2 for every spot: what a
+ * scipy.optimize.nnls loop computes.  S (T, G) fp64 dense; x (rows, G) fp32 (dtype 0) or fp64 (dtype 1) with the leading
+ * dimension ld >= G.  1 <= T <= 64, T <= G <= 16384, rows T < 2^31: MCL_EUNSUPPORTED beyond, MCL_EINVAL for a malformed call.
+ * fp64 throughout, no floating-point atomics, every sum in an order that depends on G and T alone: a spot's outputs are
+ * bit-identical alone, anywhere in a batch and in a row-permuted batch.
+ *
+ * mcl_nnls_solve_waves: the spots (one wave each) a workgroup of mcl_nnls_solve takes at a time:
+ *   (155648 - 8 T^2) / (8 (T (T + 1) / 2 + ceil(T / 2))), at most 16 (7 at T = 64).
+ * mcl_nnls_gram: A (T, T) = S S^T, the upper triangle summed over g ascending and mirrored; L (T, T) the lower Cholesky
+ *   factor of A (zeros above the diagonal).  status[0] = 1 + the first type whose pivot is not above T eps A_jj (L is
+ *   unfinished then), status[1] = 1 + the first type with a NaN or Inf in its signature (no factor then); 0 = none.
+ * mcl_nnls_products: c (rows, T) = x S^T and q (rows,) = x . x on the fp64 MFMA, x read once.  status[0] = 0, or
+ *   2^32 - 1 - r as an unsigned word for the first row r that holds a non-finite entry.
+ * mcl_nnls_solve: Lawson-Hanson's active-set method on (A, c_i), one wave per spot: from b = 0, P empty, w = c; the
+ *   largest w_j outside P enters (ties: the smaller j) until P is full or that w_j <= 10 T eps max|c_i|; A_PP z = c_P by the
+ *   Cholesky factor of A_PP, a row appended per entering index and recomputed from the first removed position on; z_P > 0
+ *   is accepted, else b steps to the boundary (alpha = min b_j / (b_j - z_j) over z_j <= 0) and every index with b_j <= 0
+ *   leaves with b_j = 0 exactly; an entering index whose own z_j <= 0 leaves at once with w_j = 0.  At most 3 T solves:
+ *   beyond, or where a pivot of A_PP is not above T eps A_jj, the spot keeps its last feasible iterate with converged = 0.
+ *   coef (rows, T) fp64, n_iter (rows,) int32 (the solves), converged (rows,) uint8.
+ * mcl_nnls_residual: rnorm (rows,) = || x_i - S^T b_i ||_2 summed from x itself, r2 = 1 - rnorm^2 / q (NaN where q = 0),
+ *   proportions (rows, T) = coef / sum(coef) (a zero row where the sum is 0), dominant (rows,) int32 = its argmax (ties:
+ *   the smaller index; -1 for a zero row). */
+int32_t mcl_nnls_solve_waves(int32_t T);
+int mcl_nnls_gram(const double* S, int32_t T, int32_t G, double* A, double* L, int32_t* status, mcl_stream_t stream);
+int mcl_nnls_products(const void* x, int64_t ld, int32_t dtype, int64_t rows, int32_t G, const double* S, int32_t T,
+                      double* c, double* q, int32_t* status, mcl_stream_t stream);
+int mcl_nnls_solve(const double* A, const double* c, int64_t rows, int32_t T, double* coef, int32_t* n_iter,
+                   void* converged, mcl_stream_t stream);
+int mcl_nnls_residual(const void* x, int64_t ld, int32_t dtype, int64_t rows, int32_t G, const double* S, int32_t T,
+                      const double* coef, const double* q, double* rnorm, double* r2, double* proportions,
+                      int32_t* dominant, mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -306,6 +306,11 @@ PROTOTYPES = {
     "mcl_cooccur_workspace_bytes": [c_l],
     "mcl_cooccur_counts": [c_p, c_p, c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
     "mcl_cooccur_scores": [c_p, c_i, c_i, c_i, c_p, c_p, c_s],
+    "mcl_nnls_solve_waves": [c_i],
+    "mcl_nnls_gram": [c_p, c_i, c_i, c_p, c_p, c_p, c_s],
+    "mcl_nnls_products": [c_p, c_l, c_i, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "mcl_nnls_solve": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_s],
+    "mcl_nnls_residual": [c_p, c_l, c_i, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -326,7 +331,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_gmm_workspace_bytes": C.c_int64, "mcl_cluster_validity_workspace_bytes": C.c_int64,
              "mcl_hmrf_workspace_bytes": C.c_int64, "mcl_ligrec_columns": c_i, "mcl_ligrec_chunk": c_i,
              "mcl_ligrec_workspace_bytes": C.c_int64, "mcl_nhood_tile_rows": c_i, "mcl_nhood_staged": c_i,
-             "mcl_nhood_workspace_bytes": C.c_int64, "mcl_cooccur_workspace_bytes": C.c_int64}
+             "mcl_nhood_workspace_bytes": C.c_int64, "mcl_cooccur_workspace_bytes": C.c_int64,
+             "mcl_nnls_solve_waves": c_i}
 
 
 def _signature(name: str):
