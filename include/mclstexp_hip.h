@@ -1515,6 +1515,52 @@ int mcl_nnls_residual(const void* x, int64_t ld, int32_t dtype, int64_t rows, in
                       const double* coef, const double* q, double* rnorm, double* r2, double* proportions,
                       int32_t* dominant, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- local spatial statistics (ABI 13, entry points added;
+ * csrc/hotspot.hip).  Local Moran's I_i, Getis-Ord Gi*, quadrant and hot / cold spot label of every (spot,
+ * column pair) with a conditional permutation test, on the graph mcl_spatial_lattice writes (nbr, w (rows, k); a slot with
+ * w = 0 is pruned; the kept slots of a row share one weight).  Slide s owns rows offsets[s] .. offsets[s + 1] (device int64,
+ * S + 1 entries); 2 <= n_s <= max_n <= 16384, 1 <= k <= 64, G <= 16384, M <= 16384 pairs, n_perms <= 65535, S <= 65535:
+ * anything else is MCL_EINVAL before a launch.  pairs (M, 2) device int32: (held column a, lagged column b); a == b is the
+ * univariate case.  x (rows, G), dtype 0 fp32 / 1 fp64, row stride ld.  Per-(spot, pair) arrays are (rows, M).  status
+ * (S, 4), zeroed by the caller: offsets that break the statements, non-finite values of x, pair columns outside 0 .. G - 1,
+ * replayed draws that do not fit the graph.  fp64, no contraction, no floating-point atomics, deterministic; a slide inside
+ * a batch is bit-identical to the same slide alone.
+ *
+ * mcl_hotspot_columns: the lagged columns a workgroup of mcl_hotspot_permute takes for a slide of n rows (1 .. 6).
+ * mcl_hotspot_table_bytes: the draw table: uint16 (n_perms, n_s, k) per slide at element offset n_perms * k * offsets[s].
+ * mcl_hotspot_moments: mean and den = sum (x - mean)^2 (2, S, M) of the held (plane 0) and the lagged (plane 1) column of
+ *   every pair in the fixed row order of mcl_spatial_stats (bit-equal to its mean / den); a constant column has den = 0.
+ * mcl_hotspot_draws: materialises the draws: entry (p, i, t) is the t-th of the d_i = min(kept slots, n - 1) distinct spots
+ *   other than i drawn for spot i in draw p, a function of (seed, p, i, n, d_i) alone; slots t >= d_i hold 0xFFFF.
+ * mcl_hotspot_permute: lag (rows, M) = sum of the centred lagged column over the kept slots in slot order; with n_perms > 0
+ *   the same sum over each draw in draw order: count_ge / count_le = #(L^p >= / <= L), sum1 = sum L^p, sum2 = sum (L^p)^2 over
+ *   p ascending.  table = NULL: the draws are generated in the kernel from seed; else they are read from the table.
+ *   deg / wbar (rows,): kept slots and their common weight.  column_mask: bit c set = launch the c-column kernel.
+ * mcl_hotspot_finalise: local_i = (n - 1) z_a (wbar lag) / den_a (a != b: / sqrt(den_a den_b)); quadrant int8 1 HH, 2 LH,
+ *   3 LL, 4 HL, 0 where a sign is zero; gi_z = (z + lag) / (sqrt(den / n) sqrt((d + 1)(n - d - 1) / (n - 1))) (a == b only,
+ *   NaN at n = d + 1), its one-tailed normal p and -log10 p in log space; with n_perms > 0 pval_sim = (min(count_ge,
+ *   count_le) + 1) / (n_perms + 1), mean_sim / var_sim / z_sim of the sims of local_i, cluster int8 = quadrant where
+ *   pval_sim <= alpha else 0.  A constant column: NaN in every floating output, 0 in quadrant and cluster. */
+int32_t mcl_hotspot_columns(int32_t n);
+int64_t mcl_hotspot_table_bytes(int64_t rows, int32_t k, int32_t n_perms);
+int mcl_hotspot_moments(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G,
+                        int32_t max_n, const int32_t* pairs, int32_t M, double* mean, double* den, int32_t* status,
+                        mcl_stream_t stream);
+int mcl_hotspot_draws(const int64_t* offsets, int32_t S, int64_t rows, int32_t max_n, int32_t k, const double* w,
+                      int32_t n_perms, uint64_t seed, void* table, mcl_stream_t stream);
+int mcl_hotspot_permute(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G,
+                        int32_t max_n, int32_t k, int32_t column_mask, const int32_t* nbr, const double* w,
+                        const int32_t* pairs, int32_t M, const double* mean, const double* den, const void* table,
+                        int32_t n_perms, uint64_t seed, double* lag, int32_t* count_ge, int32_t* count_le, double* sum1,
+                        double* sum2, int32_t* deg, double* wbar, int32_t* status, mcl_stream_t stream);
+int mcl_hotspot_finalise(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G,
+                         int32_t max_n, const int32_t* pairs, int32_t M, const double* mean, const double* den,
+                         const int32_t* deg, const double* wbar, const double* lag, const int32_t* count_ge,
+                         const int32_t* count_le, const double* sum1, const double* sum2, int32_t n_perms, double alpha,
+                         double* local_i, void* quadrant, double* gi_z, double* gi_pval_norm, double* gi_neglog10_pval_norm,
+                         double* pval_sim, double* mean_sim, double* var_sim, double* z_sim, void* cluster,
+                         mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -311,6 +311,14 @@ PROTOTYPES = {
     "mcl_nnls_products": [c_p, c_l, c_i, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
     "mcl_nnls_solve": [c_p, c_p, c_l, c_i, c_p, c_p, c_p, c_s],
     "mcl_nnls_residual": [c_p, c_l, c_i, c_l, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_hotspot_columns": [c_i],
+    "mcl_hotspot_table_bytes": [c_l, c_i, c_i],
+    "mcl_hotspot_moments": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_s],
+    "mcl_hotspot_draws": [c_p, c_i, c_l, c_i, c_i, c_p, c_i, C.c_uint64, c_p, c_s],
+    "mcl_hotspot_permute": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i,
+                            C.c_uint64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
+    "mcl_hotspot_finalise": [c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p,
+                             c_i, c_d, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_s],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -332,7 +340,7 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_hmrf_workspace_bytes": C.c_int64, "mcl_ligrec_columns": c_i, "mcl_ligrec_chunk": c_i,
              "mcl_ligrec_workspace_bytes": C.c_int64, "mcl_nhood_tile_rows": c_i, "mcl_nhood_staged": c_i,
              "mcl_nhood_workspace_bytes": C.c_int64, "mcl_cooccur_workspace_bytes": C.c_int64,
-             "mcl_nnls_solve_waves": c_i}
+             "mcl_nnls_solve_waves": c_i, "mcl_hotspot_columns": c_i, "mcl_hotspot_table_bytes": C.c_int64}
 
 
 def _signature(name: str):
