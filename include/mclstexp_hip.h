@@ -1561,6 +1561,45 @@ int mcl_hotspot_finalise(const void* x, int64_t ld, int32_t dtype, const int64_t
                          double* pval_sim, double* mean_sim, double* var_sim, double* z_sim, void* cluster,
                          mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- rank agreement of predictions (csrc/rank.hip; added
+ * under ABI 13: new entry points only).  Spearman's rho and Kendall's tau-b of pred against truth, the two other values of
+ * ``func`` in the reference's get_R(data1, data2, dim, func) (utils.py:52-65), on both ``dim``s.  pred, truth: rows x G,
+ * leading dimensions ld_pred / ld_true (elements), dtype codes 0 = fp32, 1 = fp64, each its own.
+ *   axis 0 (genes, dim=1): problem (s, g) = column g over the rows offsets[s] .. offsets[s + 1] (device-resident int64, as
+ *     for mcl_expr_metrics); S * G problems, problem index s * G + g; max_n = the largest segment (sizes the launch: a
+ *     segment that is longer, shorter than 2 or leaves the rows sets status[3 s + 2] and keeps n = 0 in its problems).
+ *   axis 1 (spots, dim=0): problem i = row i over the G genes; rows problems; offsets is not read (may be NULL), S = 1,
+ *     max_n = G.
+ * Limits: mcl_rank_max_elements(pred_dtype, true_dtype) elements per vector = 16384 when both sides are fp32, 8192 with an
+ *   fp64 side (what the LDS plan of a workgroup holds; -1 for an unknown dtype code); G <= 16384; S <= 65535; MCL_EINVAL
+ *   beyond.  mcl_rank_columns(n, ...) = the problems of n elements one workgroup takes (-1 outside 2 .. the limit).
+ * mcl_rank_stats: ints[problems x 12] int64, exact: { n, Sxy = sum a_x a_y with a = twice the 1-based average rank (-0.0
+ *   ties +0.0), then over the tie runs t of pred / truth: Tx, Ty = sum (t^3 - t); xtie, ytie = sum t(t-1)/2; x0, y0 = sum
+ *   t(t-1)(t-2); x1, y1 = sum t(t-1)(2t+5); joint = the pairs i < j tied on both sides; s = sum_{i<j} sign(a_x[i] - a_x[j])
+ *   sign(a_y[i] - a_y[j]) }.  joint and s are 0 when tau == 0 (the O(n^2) pair walk is skipped).
+ *   status[S x 3] int32 (zeroed by the call): the non-finite values met, 0x7fffffff - the smallest problem index within
+ *   the segment (gene; row for axis 1) that holds one, and the refused flag.  A non-finite value never faults; the
+ *   outputs of its segment are then unspecified.
+ * mcl_rank_finish: per problem, fp64 without contraction, NaN where n < 2 or a side is constant:
+ *   rho = (n Sxy - n^2 (n+1)^2) / (sqrt(d_x) sqrt(d_y)), d = n (n^3 - n - T) / 3, clipped to [-1, 1]; exactly +-1 where
+ *   numerator^2 = d_x d_y (perfect agreement, decided on the integers; the same rule for tau_b);
+ *   tau_b = s / (sqrt(n0 - xtie) sqrt(n0 - ytie)), n0 = n (n-1) / 2, clipped; tau_p = erfc(|z| / sqrt 2), z = s / sqrt(var),
+ *   var = (m (2n+5) - x1 - y1) / 18 + 2 xtie ytie / m + x0 y0 / (9 m (n-2)), m = n (n-1) (scipy.stats.kendalltau,
+ *   method="asymptotic"); tau_neglog10p in log space, finite where tau_p underflows; both NaN at n < 3.  With tau == 0
+ *   only rho is written (the tau pointers may be NULL).  Spearman's p is mcl_pearson_pvalue of rho.
+ * mcl_rank_summary: rho, tau_b (S x G; tau_b may be NULL), heg (S x n_heg) as mcl_expr_metrics writes it -> summary[S x 5]
+ *   = { heg_rho = mean of rho over heg (NaN propagates, np.mean), hvg_rho = mean over the non-NaN genes (NaN if none),
+ *   heg_tau, hvg_tau (NaN without tau_b), n_valid }, every sum in gene-index order.                                  */
+int32_t mcl_rank_max_elements(int32_t pred_dtype, int32_t true_dtype);
+int32_t mcl_rank_columns(int32_t n, int32_t pred_dtype, int32_t true_dtype);
+int mcl_rank_stats(const void* pred, int64_t ld_pred, int32_t pred_dtype, const void* truth, int64_t ld_true,
+                   int32_t true_dtype, const int64_t* offsets, int32_t S, int64_t rows, int32_t G, int32_t max_n,
+                   int32_t axis, int32_t tau, int64_t* ints, int32_t* status, mcl_stream_t stream);
+int mcl_rank_finish(const int64_t* ints, int64_t problems, int32_t tau, double* rho, double* tau_b, double* tau_p,
+                    double* tau_neglog10p, mcl_stream_t stream);
+int mcl_rank_summary(const double* rho, const double* tau_b, const int64_t* heg, int32_t S, int32_t G, int32_t n_heg,
+                     double* summary, mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

@@ -196,6 +196,15 @@ def load_gene_major(paths: Sequence[str]) -> List[np.ndarray]:
     return [a.T for a in mats]
 
 
+def json_value(v):
+    """``v`` as ``json`` can write it: a NaN float as None, an array as a list of Python numbers (NaN entries None)."""
+    if isinstance(v, float) and v != v:
+        return None
+    if isinstance(v, np.ndarray):
+        return [json_value(float(x)) if v.dtype.kind == "f" else int(x) for x in v]
+    return v
+
+
 def write_json(path: str, doc) -> None:
     with open(path, "w") as fh:
         json.dump(doc, fh, indent=1)
