@@ -1600,6 +1600,37 @@ int mcl_rank_finish(const int64_t* ints, int64_t problems, int32_t tau, double* 
 int mcl_rank_summary(const double* rho, const double* tau_b, const int64_t* heg, int32_t S, int32_t G, int32_t n_heg,
                      double* summary, mcl_stream_t stream);
 
+/* ---------------------------------------------------------------- gene programs: batched NMF (csrc/nmf.hip)
+ * X ~ W H with W, H >= 0 by scikit-learn's multiplicative-update solver (non_negative_factorization(solver="mu"), no
+ * regularisation), for every row segment of a row-stacked x (rows, G; dtype 0 fp32 / 1 fp64, leading dimension ld >= G,
+ * offsets device int64 [S + 1]) times every one of n_init starts per call.  Problem p = segment * n_init + start; W is
+ * (n_init, rows, k), H is (S n_init, k, G), both fp64 and updated in place; active (S n_init) int32 is 1 for a problem that
+ * still iterates (the caller sets it; a problem whose word is 0 is frozen: no kernel touches it).  loss: 0 Frobenius,
+ * 1 Kullback-Leibler.  1 <= k <= 64, G <= 16384, S n_init <= 65535, rows k < 2^31: MCL_EUNSUPPORTED beyond (-1 from
+ * mcl_nmf_workspace_bytes), MCL_EINVAL for a malformed call.  fp64 throughout, no floating-point atomics; every sum runs
+ * in an order fixed by the segment's rows, G and k.  work holds mcl_nmf_workspace_bytes bytes (the same arguments).
+ * mcl_nmf_check: status[0] = 0, or 0xFFFFFFFF - the first row of x that holds a negative or non-finite value.
+ * mcl_nmf_steps: n_steps iterations.  Per iteration W <- W o (X H^T) / (W (H H^T)) then, where update_h, H <- H o (W^T X) /
+ *   ((W^T W) H) from the new W (Frobenius); W <- W o ((X / WH) H^T) / rowsum(H), H <- H o (W^T (X / WH)) / colsum(W) and
+ *   H < 2^-52 -> 0 (KL).  WH below EPSILON = 2^-23 is EPSILON, a zero denominator is EPSILON (colsum(W) = 0: 1).
+ * mcl_nmf_error: error = sqrt(2 D(X | W H)) summed from x itself, and by phase: 0 the error at init; 1 the check of
+ *   iteration it -- a live problem with (previous - error) / error_at_init < tol is frozen (active = 0, n_iter = it,
+ *   converged = it < max_iter), else previous = error; 2 the final error of every problem.  record (S n_init, 8) fp64:
+ *   { error at init, previous, last, n_iter, converged, final, 0, 0 }; history (S n_init, hist_len): slot it / 10.
+ * mcl_nmf_programs: for one W (rows, k) and H (S, k, G): hsum = rowsum(H), programs = H / hsum (0 where hsum = 0),
+ *   usage = W o hsum, dominant = argmax of usage (ties: the smaller index; -1 for a zero row).                            */
+int64_t mcl_nmf_workspace_bytes(int64_t rows, int32_t G, int32_t k, int32_t S, int32_t n_init, int32_t max_n, int32_t loss);
+int mcl_nmf_check(const void* x, int64_t ld, int32_t dtype, int64_t rows, int32_t G, int32_t* status, mcl_stream_t stream);
+int mcl_nmf_steps(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int32_t n_init, int64_t rows,
+                  int32_t G, int32_t k, int32_t max_n, int32_t loss, int32_t update_h, double* W, double* H, double* work,
+                  int32_t* active, int32_t n_steps, mcl_stream_t stream);
+int mcl_nmf_error(const void* x, int64_t ld, int32_t dtype, const int64_t* offsets, int32_t S, int32_t n_init, int64_t rows,
+                  int32_t G, int32_t k, int32_t max_n, int32_t loss, const double* W, const double* H, double* work,
+                  int32_t* active, int32_t phase, int32_t it, double tol, int32_t max_iter, double* record, double* history,
+                  int32_t hist_len, mcl_stream_t stream);
+int mcl_nmf_programs(const double* W, const double* H, const int64_t* offsets, int32_t S, int64_t rows, int32_t G, int32_t k,
+                     int32_t max_n, double* hsum, double* programs, double* usage, int32_t* dominant, mcl_stream_t stream);
+
 /* ---------------------------------------------------------------- input pipeline on the GPU
  * mcl_patch_gather: the reference's per-spot patch extraction (dataset.py:226-231 PIL crop + transforms.ToTensor;
  *   dataset.py:330-336 numpy crop of the cv2 image + TenxDataset.transform) for a whole batch: image_u8 (Hs, Ws, 3)

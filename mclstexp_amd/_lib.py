@@ -324,6 +324,12 @@ PROTOTYPES = {
     "mcl_rank_stats": [c_p, c_l, c_i, c_p, c_l, c_i, c_p, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_s],
     "mcl_rank_finish": [c_p, c_l, c_i, c_p, c_p, c_p, c_p, c_s],
     "mcl_rank_summary": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_s],
+    "mcl_nmf_workspace_bytes": [c_l, c_i, c_i, c_i, c_i, c_i, c_i],
+    "mcl_nmf_check": [c_p, c_l, c_i, c_l, c_i, c_p, c_s],
+    "mcl_nmf_steps": [c_p, c_l, c_i, c_p, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_s],
+    "mcl_nmf_error": [c_p, c_l, c_i, c_p, c_i, c_i, c_l, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_d, c_i, c_p, c_p,
+                      c_i, c_s],
+    "mcl_nmf_programs": [c_p, c_p, c_p, c_i, c_l, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_s],
 }
 _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_gemm_args_size": C.c_uint32,
              "mcl_gemm_args_min_size": C.c_uint32, "mcl_gemm_auto_ksplit": c_i, "mcl_proj_head_ksplit": c_i,
@@ -346,7 +352,8 @@ _RESTYPES = {"mcl_abi_version": C.c_int, "mcl_error_string": C.c_char_p, "mcl_ge
              "mcl_ligrec_workspace_bytes": C.c_int64, "mcl_nhood_tile_rows": c_i, "mcl_nhood_staged": c_i,
              "mcl_nhood_workspace_bytes": C.c_int64, "mcl_cooccur_workspace_bytes": C.c_int64,
              "mcl_nnls_solve_waves": c_i, "mcl_hotspot_columns": c_i, "mcl_hotspot_table_bytes": C.c_int64,
-             "mcl_rank_max_elements": c_i, "mcl_rank_columns": c_i}
+             "mcl_rank_max_elements": c_i, "mcl_rank_columns": c_i,
+             "mcl_nmf_workspace_bytes": C.c_int64}
 
 
 def _signature(name: str):

@@ -2,7 +2,8 @@
 (or domain) expression signatures, ``b_i = argmin over b >= 0 of || x_i - S^T b ||_2`` -- the NNLS baseline of the
 deconvolution benchmarks, what a ``scipy.optimize.nnls`` loop over the spots computes -- for all slides per call, and the
 number the feature exists for: does the predicted expression imply the same tissue composition as the measured expression
-(``deconvolution_recovery``)?  The signatures are given, or pooled from annotated slides (``signatures_from_groups``).
+(``deconvolution_recovery``)?  The signatures are given, pooled from annotated slides (``signatures_from_groups``), or found
+without labels: ``nmf.nmf(x, k)["programs"][segment]`` is a (T, G) signature matrix that ``nnls`` accepts as it is.
 
 What is computed is stated in DESIGN 6.21 and restated in numpy by ``tests/deconv_reference.py``, which is pinned to
 ``scipy.optimize.nnls``.  Parity with SPOTlight, RCTD or cell2location is unpinned, and no signature set is shipped or
