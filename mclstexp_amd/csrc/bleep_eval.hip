@@ -15,6 +15,7 @@
 // No floating-point atomics; every reduction order depends only on the problem's own shape (k, dim, G, the segment's length):
 // a segment scored inside a batch is bit-identical to the same segment scored alone.
 #include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -193,8 +194,6 @@ void launch_cell_pearson(const void* pred, long long ldp, const void* tru, long 
 constexpr int GS_WAVES = 4;
 constexpr int GS_UNROLL = 4;      // rows per wave per trip
 constexpr int BS_THREADS = 256;
-constexpr int BS_SAMPLE = 256;    // genes in the sample that sets the candidate threshold
-constexpr int BS_CAP = 2048;      // candidates ranked in LDS; more -> ranked against all G values in global memory
 
 // np.sum(true, axis=0) and np.var(true, axis=0) of one segment: lane = gene, the waves stride over the rows
 template <typename TT>
@@ -251,97 +250,23 @@ __global__ __launch_bounds__(GS_WAVES * 64) void truth_gene_stats_kernel(const T
   }
 }
 
-// (vj, gj) comes before (v, g) in the tail of a stable ascending argsort read backwards: larger value, equal values by
-// DESCENDING gene index
-__device__ __forceinline__ int bs_beats(double vj, int gj, double v, int g) { return (vj > v) || (vj == v && gj > g); }
-
-struct bs_lds {
-  double smp_v[BS_SAMPLE];
-  double cand_v[BS_CAP];
-  int smp_g[BS_SAMPLE];
-  int cand_g[BS_CAP];
-  int wave_cnt[BS_THREADS / 64];
-  double thr;
-};
-
-// top[rank] = the gene of that rank for rank < n_top (entries no rank reaches -- non-finite values only -- stay -1)
-__device__ void bs_top_genes(const double* __restrict__ val, int G, int n_top, long long* __restrict__ top, bs_lds& L) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  for (int i = tid; i < n_top; i += BS_THREADS) top[i] = -1;
-  // 1. threshold T = the n_top-th largest of an evenly strided sample: the full set's n_top-th largest is >= T
-  const int ns = min(G, BS_SAMPLE);
-  if (tid == 0) L.thr = -INFINITY;
-  if (tid < ns) {
-    const int gs = (int)(((long long)tid * G) / ns);
-    L.smp_v[tid] = val[gs];
-    L.smp_g[tid] = gs;
-  }
-  __syncthreads();
-  if (n_top <= ns && tid < ns) {
-    const double vt = L.smp_v[tid];
-    const int gt = L.smp_g[tid];
-    int rank = 0;
-    for (int j = 0; j < ns; ++j) rank += bs_beats(L.smp_v[j], L.smp_g[j], vt, gt);
-    if (rank == n_top - 1) L.thr = vt;
-  }
-  __syncthreads();
-  const double T = L.thr;
-  // 2. candidates (value >= T) compacted in gene order: ballot + a prefix over the waves
-  int count = 0;
-  for (int g0 = 0; g0 < G; g0 += BS_THREADS) {
-    const int g = g0 + tid;
-    const double vg = val[g < G ? g : G - 1];
-    const bool f = g < G && vg >= T;
-    const unsigned long long b = __ballot(f);
-    if (lane == 0) L.wave_cnt[w] = __builtin_popcountll(b);
-    __syncthreads();
-    int before = count;
-    for (int v = 0; v < w; ++v) before += L.wave_cnt[v];
-    if (f) {
-      const int pos = before + (int)lanes_below(b);
-      if (pos < BS_CAP) {
-        L.cand_v[pos] = vg;
-        L.cand_g[pos] = g;
-      }
-    }
-    for (int v = 0; v < BS_THREADS / 64; ++v) count += L.wave_cnt[v];
-    __syncthreads();
-  }
-  // 3. exact rank of every candidate among the candidates (a non-candidate is strictly below every candidate)
-  if (count <= BS_CAP) {
-    for (int c = tid; c < count; c += BS_THREADS) {
-      const double vc = L.cand_v[c];
-      const int gc = L.cand_g[c];
-      int rank = 0;
-      for (int j = 0; j < count; ++j) rank += bs_beats(L.cand_v[j], L.cand_g[j], vc, gc);
-      if (rank < n_top) top[rank] = gc;
-    }
-  } else {
-    for (int g = tid; g < G; g += BS_THREADS) {
-      const double vg = val[g];
-      if (!(vg >= T)) continue;
-      int rank = 0;
-      for (int j = 0; j < G; ++j) rank += bs_beats(val[j], j, vg, g);
-      if (rank < n_top) top[rank] = g;
-    }
-  }
-  __syncthreads();  // top[] is read back by the caller; the LDS is free again
-}
-
 __global__ __launch_bounds__(BS_THREADS) void bleep_summary_kernel(
     const long long* __restrict__ offsets, int G, int n_top, const double* __restrict__ r_gene_all,
     const double* __restrict__ r_cell, const int* __restrict__ markers, int n_markers,
     const double* __restrict__ gene_sum, const double* __restrict__ gene_var, long long* __restrict__ top_sum_all,
     long long* __restrict__ top_var_all, double* __restrict__ summary) {
-  __shared__ bs_lds L;
+  __shared__ stats::top_lds<BS_THREADS> L;
   __shared__ double red[8][BS_THREADS];
   const int tid = threadIdx.x;
   const int s = blockIdx.x;
   const double* rr = r_gene_all + (long long)s * G;
   long long* top_sum = top_sum_all + (long long)s * n_top;
   long long* top_var = top_var_all + (long long)s * n_top;
-  bs_top_genes(gene_sum + (long long)s * G, G, n_top, top_sum, L);
-  bs_top_genes(gene_var + (long long)s * G, G, n_top, top_var, L);
+  // equal values to the HIGHER gene index; a rank that no gene reaches (non-finite values only) stays -1
+  for (int i = tid; i < n_top; i += BS_THREADS) top_sum[i] = -1;
+  stats::top_select<stats::DESCENDING_HIGH>(gene_sum + (long long)s * G, G, n_top, top_sum, L);
+  for (int i = tid; i < n_top; i += BS_THREADS) top_var[i] = -1;
+  stats::top_select<stats::DESCENDING_HIGH>(gene_var + (long long)s * G, G, n_top, top_var, L);
 
   // per-thread strided sums, then a fixed LDS tree
   const long long r0 = offsets[s], r1 = offsets[s + 1];

@@ -51,13 +51,6 @@ __device__ __forceinline__ double nn_bcast(double v, int src) {
   const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), src);
   return __longlong_as_double((long long)(((u64)hi << 32) | lo));
 }
-// LDS written by some lanes of a wave is read by others: the hardware runs a wave's LDS instructions in order, this keeps the
-// compiler from moving them across
-__device__ __forceinline__ void nn_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // ------------------------------------------------------------------------------------------------------------- gram
 __global__ __launch_bounds__(NN_GRAM_THREADS) void nn_gram_kernel(const double* __restrict__ S, int T, int G,
@@ -229,7 +222,7 @@ __device__ __forceinline__ bool nn_append(const double* a_s, double* tri, int* p
   }
   if (lane == j) s.pos = m;
   s.m = m + 1;
-  nn_wave_sync();
+  wave_sync();
   return true;
 }
 
@@ -324,9 +317,9 @@ __global__ __launch_bounds__(NN_MAX_WAVES * 64) void nn_solve_kernel(const doubl
         const int np = __shfl(landing, s.pos < 0 ? 0 : s.pos, 64);
         if (in_p) s.pos = leave ? -1 : np;
         const int m2 = __popcll(keep);
-        nn_wave_sync();
+        wave_sync();
         if (lane < m2) s.pidx = plist[lane];
-        nn_wave_sync();
+        wave_sync();
         s.m = first_gone;                                      // rows ahead of the first removed position stand
         bool okf = true;
         for (int p = first_gone; p < m2 && okf; ++p)

@@ -146,6 +146,13 @@ __device__ __forceinline__ int opaque_lane(int lane) {
   asm volatile("" : "+v"(lane));
   return lane;
 }
+// LDS written by some lanes of a wave is read by others: the hardware runs a wave's LDS instructions in order, this keeps the
+// compiler from moving them across
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 // ---- order-preserving bit patterns: a < b <=> order_key(a) < order_key(b), -0.0 just below +0.0; a NaN with the sign bit
 // clear sorts above +inf (as torch.topk treats it).  key_value is the inverse.

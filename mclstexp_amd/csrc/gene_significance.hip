@@ -16,6 +16,7 @@
 //   gene_order_kernel      gridded over genes: the exact descending rank of every gene by counting against all G means
 //                          (staged through LDS in tiles), ties to the lower gene index, NaN means last.
 #include "common.h"
+#include "stats.h"
 #include "betacf.h"   // log_betacf_sym, CF_MAX_ITER
 
 namespace {
@@ -45,9 +46,9 @@ __global__ __launch_bounds__(PV_THREADS) void pearson_pvalue_kernel(const double
     const double a = 0.5 * (double)n - 1.0;
     const double x = 0.5 * (1.0 - fabs(r));
     const double pre = lgamma(2.0 * a) - 2.0 * lgamma(a) + a * log(x) + a * log1p(-x) - log(a);
-    double lp = 0.6931471805599453 + pre + log_betacf_sym(a, x);
+    double lp = stats::LN2 + pre + log_betacf_sym(a, x);
     lp = lp > 0.0 ? 0.0 : lp;          // p <= 1 (rounding at r ~ 0); NaN passes through
-    nl = 0.0 - lp / 2.302585092994046;
+    nl = 0.0 - lp / stats::LN10;
     p = exp(lp);
   }
   p_out[o] = p;
@@ -88,6 +89,7 @@ __device__ __forceinline__ int sorts_before(double mj, int gj, double m, int g) 
   return (mj > m) || (mj == m && gj < g);
 }
 
+// (the counting loop is written out in every kernel that has it: stats.h says why it holds no shared form)
 __global__ __launch_bounds__(RANK_THREADS) void gene_order_kernel(const double* __restrict__ mean, int G,
                                                                   long long* __restrict__ order) {
   __shared__ double tile[RANK_THREADS];

@@ -24,6 +24,7 @@
 // contraction), no floating-point atomics, no workgroup waits for another: a slide inside a batch is bit-identical to the
 // same slide alone, whatever the launch shape.
 #include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -38,9 +39,6 @@ constexpr int HS_CMAX = 6;               // lagged columns per workgroup, as csr
 constexpr int HS_Z_BYTES = 155648;       // LDS for the centred columns (152 KiB of the 160), as SP_Z_BYTES
 constexpr int HS_O_THREADS = 256;
 constexpr int HS_STATUS = 4;             // offsets broken, non-finite x, pair column out of range, draws that do not fit
-constexpr double HS_LN10 = 2.302585092994046;
-constexpr double HS_LN2 = 0.6931471805599453;
-constexpr double HS_SQRT2 = 1.4142135623730951;
 
 __host__ __device__ inline long long hs_align8(long long v) { return (v + 7) & ~7ll; }
 __host__ __device__ inline int hs_columns(int n) {
@@ -54,15 +52,6 @@ constexpr int hs_threads() { return KD <= 8 ? 1024 : 256; }
 // x (rows, G) in either width, as fp64
 __device__ __forceinline__ double hs_ld(const void* x, int dtype, long long idx) {
   return dtype ? static_cast<const double*>(x)[idx] : (double)static_cast<const float*>(x)[idx];
-}
-
-// p = sf(|z|) of the standard normal and -log10 p in log space: the one-tailed branch of spatial.hip's sp_normal_tail
-__device__ __forceinline__ void hs_normal_tail(double z, double* p_out, double* nl_out) {
-#pragma clang fp contract(off)
-  const double az = fabs(z) / HS_SQRT2;
-  const double p = 0.5 * erfc(az);
-  *p_out = p;
-  *nl_out = az < 1.0 ? 0.0 - log10(p) : ((az * az - log(erfcx(az))) + HS_LN2) / HS_LN10;
 }
 
 // the d <= KD distinct spots of draw h = mix(mix(mix(seed) ^ p) + i) for spot i of n, none of them i: Floyd's algorithm.
@@ -325,7 +314,7 @@ __global__ __launch_bounds__(HS_O_THREADS) void hs_final_kernel(
     const double sd = sqrt(da / (double)n);
     const double sc = sqrt(((double)(d + 1) * (double)(n - d - 1)) / (double)(n - 1));
     gz = (za + L) / (sd * sc);
-    hs_normal_tail(gz, &gp, &gl);
+    stats::normal_tail(gz, 0, &gp, &gl);
   }
   gi_z[o] = gz;
   gi_p[o] = gp;

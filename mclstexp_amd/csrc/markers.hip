@@ -25,11 +25,12 @@
 //   marker_test_kernel    one lane per (slide, group, gene): score, p, -log10 p (log space), log fold change.
 //   marker_prank_kernel / marker_bh_kernel / marker_order_kernel
 //                         Benjamini-Hochberg and the score order per (slide, group) by exact counting ranks against all G
-//                         keys (value, gene index), as gene_order_kernel of gene_significance.hip: ties go to the lower
-//                         gene index without a stable sort.  The suffix minimum of BH is a min-scan (order-free).
+//                         keys (value, gene index), BH by stats.h's bh_adjust: ties go to the lower gene index
+//                         without a stable sort.  The suffix minimum of BH is a min-scan (order-free).
 // No floating-point atomics, no workgroup waits for another, every fp64 sum's order depends on the slide alone: a slide
 // inside a batch is bit-identical to the same slide alone.
 #include "common.h"
+#include "stats.h"
 #include "betacf.h"
 
 namespace {
@@ -360,7 +361,6 @@ __global__ __launch_bounds__(MK_RANK_THREADS) void marker_rank_kernel(
 }
 
 // -------------------------------------------------------------------------------------------------------------- test
-constexpr double MK_LN10 = 2.302585092994046;
 constexpr double MK_LGAMMA_HALF = 0.5723649429247001;     // log sqrt(pi)
 
 // two-sided p of Student's t with nu degrees of freedom, I_{nu / (nu + t^2)}(nu / 2, 1 / 2), and -log10 p in log space
@@ -375,13 +375,13 @@ __device__ void mk_student_p(double t, double nu, double* p_out, double* nl_out)
     double lp = ((a * logx + b * logy) - log(a) - logB) + log_betacf(a, b, x);
     lp = lp > 0.0 ? 0.0 : lp;
     *p_out = exp(lp);
-    *nl_out = 0.0 - lp / MK_LN10;
+    *nl_out = 0.0 - lp / stats::LN10;
   } else {                                                               // p = 1 - I_{1 - x}(1 / 2, nu / 2)
     const double y = t2 / (nu + t2);
     double lq = ((b * logy + a * logx) - log(b) - logB) + log_betacf(b, a, y);
     lq = lq > 0.0 ? 0.0 : lq;
     *p_out = 0.0 - expm1(lq);
-    *nl_out = 0.0 - log1p(0.0 - exp(lq)) / MK_LN10;
+    *nl_out = 0.0 - log1p(0.0 - exp(lq)) / stats::LN10;
   }
 }
 
@@ -411,10 +411,8 @@ __global__ __launch_bounds__(MK_T_THREADS) void marker_test_kernel(
     const double den = sqrt(c * prod / 12.0);
     double z = (0.5 * (double)num2) / den;
     if (!(den > 0.0) || isnan(z)) z = 0.0;
-    const double az = fabs(z) / 1.4142135623730951;
     score = z;
-    p = erfc(az);
-    nl = az < 1.0 ? 0.0 - log10(p) : (az * az - log(erfcx(az))) / MK_LN10;
+    stats::normal_tail(z, 1, &p, &nl);
   } else {
     const double nrr = method == 2 ? (double)ng : (double)nr;
     const double vg = var_g[o] / (double)ng, vr = var_r[o] / nrr;
@@ -437,6 +435,7 @@ __global__ __launch_bounds__(MK_T_THREADS) void marker_test_kernel(
 
 // --------------------------------------------------------------------------------------------- BH and the score order
 // rank of every gene's p ascending (NaN as 1, equal p by gene index); scratch[rank] = p G / (rank + 1)
+// (the counting loop is written out in every kernel that has it: stats.h says why it holds no shared form)
 __global__ __launch_bounds__(MK_O_THREADS) void marker_prank_kernel(const mk_slide* __restrict__ info, int G,
                                                                     const double* __restrict__ pvals,
                                                                     int* __restrict__ prank, double* __restrict__ scratch) {
@@ -459,7 +458,7 @@ __global__ __launch_bounds__(MK_O_THREADS) void marker_prank_kernel(const mk_sli
   }
   if (g < G) {
     prank[base + g] = rank;
-    scratch[base + rank] = p * ((double)G / (double)(rank + 1));
+    stats::bh_stage(scratch, base, rank, p, G);
   }
 }
 
@@ -471,30 +470,11 @@ __global__ __launch_bounds__(MK_BH_THREADS) void marker_bh_kernel(const mk_slide
   const mk_slide inf = info[blockIdx.y];
   if ((int)blockIdx.x >= inf.k) return;
   const long long base = (inf.g0 + blockIdx.x) * (long long)G;
-  const int t = threadIdx.x;
-  const int ch = (G + MK_BH_THREADS - 1) / MK_BH_THREADS;
-  const int i0 = min(G, t * ch), i1 = min(G, i0 + ch);
-  double m = INFINITY;
-  for (int i = i0; i < i1; ++i) m = fmin(m, scratch[base + i]);
-  cmin[t] = m;
-  __syncthreads();
-  for (int o = 1; o < MK_BH_THREADS; o <<= 1) {            // inclusive suffix min-scan of the chunk minima
-    const double other = t + o < MK_BH_THREADS ? cmin[t + o] : INFINITY;
-    __syncthreads();
-    cmin[t] = fmin(cmin[t], other);
-    __syncthreads();
-  }
-  double run = t + 1 < MK_BH_THREADS ? cmin[t + 1] : INFINITY;
-  for (int i = i1 - 1; i >= i0; --i) {
-    run = fmin(run, scratch[base + i]);
-    scratch[base + i] = run;
-  }
-  __threadfence_block();
-  __syncthreads();
-  for (int g = t; g < G; g += MK_BH_THREADS) adj[base + g] = fmin(1.0, scratch[base + prank[base + g]]);
+  stats::bh_adjust<MK_BH_THREADS, false>(nullptr, prank, scratch, adj, base, G, cmin);
 }
 
 // rank of every gene by descending score (or |score|), equal scores by gene index; the first n_genes are gathered
+// (the counting loop is written out in every kernel that has it: stats.h says why it holds no shared form)
 __global__ __launch_bounds__(MK_O_THREADS) void marker_order_kernel(
     const mk_slide* __restrict__ info, int G, int n_genes, int rankby_abs, const double* __restrict__ scores,
     const double* __restrict__ pvals, const double* __restrict__ adj, const double* __restrict__ nlp,

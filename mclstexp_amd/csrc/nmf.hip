@@ -43,14 +43,6 @@ constexpr int NM_HCHUNK = 32;                         // genes a workgroup of th
 constexpr int NM_RECORD = 8;                          // doubles of a problem's record
 constexpr double NM_EPSILON = 1.1920928955078125e-07; // sklearn's EPSILON = float32 eps
 
-// LDS written by some lanes of a wave is read by others: the hardware runs a wave's LDS instructions in order, this keeps the
-// compiler from moving them across
-__device__ __forceinline__ void nm_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // problem p -> (segment, start, first row, rows); 0 rows where the offsets do not fit the launch
 __device__ __forceinline__ int nm_problem(const long long* __restrict__ offsets, int p, int n_init, long long rows, int max_n,
                                           int* s, long long* r0) {
@@ -264,10 +256,10 @@ __global__ __launch_bounds__(256) void nm_update_w_kernel(const X* __restrict__ 
         const double q = xv[qi] / whc;
         qs[KL ? wv : 0][lk + 4 * qi][lm] = (row < n && okg) ? q : 0.0;
       }
-      nm_wave_sync();
+      wave_sync();
 #pragma unroll
       for (int t4 = 0; t4 < 4; ++t4) a[t4] = qs[KL ? wv : 0][lm][4 * lk + t4];
-      nm_wave_sync();
+      wave_sync();
     }
 #pragma unroll
     for (int t = 0; t < NKT; ++t)

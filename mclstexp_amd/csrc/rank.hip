@@ -31,6 +31,7 @@
 // would need 192 KiB).  No floating-point atomics, no workgroup waits for another; every output of a problem is a function of
 // its own two vectors: a slide inside a batch is bit-identical to it alone, a row-permuted slide gives the same bits.
 #include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -46,8 +47,6 @@ constexpr int RK_STATUS = 3;           // int32 per slide: non-finite values, 0x
 constexpr int RK_F_THREADS = 256;
 constexpr int RK_S_THREADS = 256;
 constexpr int RK_S_TILE = 1024;
-constexpr double RK_SQRT2 = 1.4142135623730951;
-constexpr double RK_LN10 = 2.302585092994046;
 
 enum { I_N, I_SXY, I_TX, I_TY, I_XTIE, I_YTIE, I_X0, I_Y0, I_X1, I_Y1, I_JOINT, I_S };
 
@@ -282,15 +281,6 @@ __global__ __launch_bounds__(RK_THREADS) void rank_pair_kernel(
   for (int e = tid; e < Cc * RK_INTS; e += RK_THREADS) ints[(q_base + j0) * RK_INTS + e] = (long long)acc[e];
 }
 
-// p = 2 sf(|z|) of the standard normal and -log10 p in log space (spatial.hip's sp_normal_tail, two-tailed)
-__device__ __forceinline__ void rk_normal_tail(double z, double* p_out, double* nl_out) {
-#pragma clang fp contract(off)
-  const double az = fabs(z) / RK_SQRT2;
-  const double e = erfc(az);
-  *p_out = e;
-  *nl_out = az < 1.0 ? 0.0 - log10(e) : (az * az - log(erfcx(az))) / RK_LN10;
-}
-
 __device__ __forceinline__ double rk_clip(double v) { return v > 1.0 ? 1.0 : (v < -1.0 ? -1.0 : v); }
 // num / (sqrt(a) sqrt(b)) clipped to [-1, 1], a, b > 0, |num| <= sqrt(a b) < 2^63.  Where num^2 = a b -- perfect agreement,
 // an exact statement about integers -- the value is +-1 and is returned as such: sqrt(a) sqrt(a) may round to a (1 + eps)
@@ -324,7 +314,7 @@ __global__ __launch_bounds__(RK_F_THREADS) void rank_finish_kernel(const long lo
           const double var = ((double)(m * (2 * n + 5) - I[I_X1] - I[I_Y1]) / 18.0 +
                               (double)(2 * I[I_XTIE] * I[I_YTIE]) / (double)m) +
                              ((double)I[I_X0] * (double)I[I_Y0]) / (double)(9 * m * (n - 2));
-          rk_normal_tail((double)s / sqrt(var), &tp, &tnl);
+          stats::normal_tail((double)s / sqrt(var), 1, &tp, &tnl);
         }
       }
     }

@@ -23,7 +23,7 @@
 //                      gathers z from LDS.  The observed statistic is the same kernel without a table (pi = identity).
 //   sp_moments_kernel / sp_prank_kernel / sp_bh_kernel / sp_summary_kernel
 //                      z and p under normality (-log10 p in log space), Benjamini-Hochberg over the genes of a slide by
-//                      exact counting ranks (the arithmetic of csrc/markers.hip, restated), and per gene the folded
+//                      exact counting ranks (stats.h, as csrc/markers.hip), and per gene the folded
 //                      permutation p, the mean and population variance of the sims summed over p in ascending order.
 //
 // THE FIXED ROW ORDER of every fp64 sum over the rows of a slide: lane r of 256 adds its rows r, r + 256, ... in ascending
@@ -32,6 +32,7 @@
 // function of n alone.  Every product and sum is rounded separately (no contraction).  No floating-point atomics, no
 // workgroup waits for another: a slide inside a batch is bit-identical to the same slide alone.
 #include "common.h"
+#include "stats.h"
 
 namespace {
 
@@ -50,9 +51,6 @@ constexpr int SP_SORT_THREADS = 1024;
 constexpr int SP_O_THREADS = 256;
 constexpr int SP_BH_THREADS = 1024;
 constexpr int SP_STATUS = 6;             // config, bad index, bad weight, duplicate neighbour, non-binary rows, non-standardised rows
-constexpr double SP_LN10 = 2.302585092994046;
-constexpr double SP_LN2 = 0.6931471805599453;
-constexpr double SP_SQRT2 = 1.4142135623730951;
 
 __host__ __device__ inline long long sp_align8(long long v) { return (v + 7) & ~7ll; }
 // workspace: permutation table uint16[n_perms * rows] | in-degree histogram int32[rows * hist_slots]
@@ -425,21 +423,6 @@ __global__ __launch_bounds__(SP_STAT_THREADS) void sp_stat_kernel(
 }
 
 // --------------------------------------------------------------------------------------------- moments, BH, summary
-// p = sf(|z|) (two_tailed: twice that) of the standard normal and -log10 p in log space
-__device__ __forceinline__ void sp_normal_tail(double z, int two_tailed, double* p_out, double* nl_out) {
-#pragma clang fp contract(off)
-  const double az = fabs(z) / SP_SQRT2;
-  const double e = erfc(az);
-  if (two_tailed) {
-    *p_out = e;
-    *nl_out = az < 1.0 ? 0.0 - log10(e) : (az * az - log(erfcx(az))) / SP_LN10;
-  } else {
-    const double p = 0.5 * e;
-    *p_out = p;
-    *nl_out = az < 1.0 ? 0.0 - log10(p) : ((az * az - log(erfcx(az))) + SP_LN2) / SP_LN10;
-  }
-}
-
 __global__ __launch_bounds__(SP_O_THREADS) void sp_moments_kernel(
     const long long* __restrict__ offsets, int S, long long rows, int G, int max_n, const double* __restrict__ consts,
     const double* __restrict__ stat, int two_tailed, double* __restrict__ zn, double* __restrict__ pv,
@@ -465,14 +448,15 @@ __global__ __launch_bounds__(SP_O_THREADS) void sp_moments_kernel(
     z = (v - 1.0) / sqrt(VC);
   }
   double p, l;
-  sp_normal_tail(z, two_tailed, &p, &l);
+  stats::normal_tail(z, two_tailed, &p, &l);
   if (n == 0 || isnan(z)) { z = NAN; p = NAN; l = NAN; }
   zn[o] = z;
   pv[o] = p;
   nl[o] = l;
 }
 
-// rank of every gene's p ascending (NaN as 1, equal p by gene index); scratch[rank] = p G / (rank + 1): csrc/markers.hip's BH
+// rank of every gene's p ascending (NaN as 1, equal p by gene index); scratch[rank] = p G / (rank + 1)
+// (the counting loop is written out in every kernel that has it: stats.h says why it holds no shared form)
 __global__ __launch_bounds__(SP_O_THREADS) void sp_prank_kernel(int G, const double* __restrict__ pvals,
                                                                 int* __restrict__ prank, double* __restrict__ scratch) {
 #pragma clang fp contract(off)
@@ -493,39 +477,18 @@ __global__ __launch_bounds__(SP_O_THREADS) void sp_prank_kernel(int G, const dou
   }
   if (g < G) {
     prank[base + g] = rank;
-    scratch[base + rank] = p * ((double)G / (double)(rank + 1));
+    stats::bh_stage(scratch, base, rank, p, G);
   }
 }
 
-// one workgroup per (statistic, slide): suffix minimum over the sorted p G / j, capped at 1, scattered back to gene order;
-// a NaN p (a constant gene) counts as p = 1 among the others and stays NaN itself
+// one workgroup per (statistic, slide): Benjamini-Hochberg in gene order; a NaN p (a constant gene) counts as p = 1 among
+// the others and stays NaN itself
 __global__ __launch_bounds__(SP_BH_THREADS) void sp_bh_kernel(int G, const double* __restrict__ pvals,
                                                               const int* __restrict__ prank, double* __restrict__ scratch,
                                                               double* __restrict__ adj) {
   __shared__ double cmin[SP_BH_THREADS];
   const long long base = (long long)blockIdx.x * G;
-  const int t = threadIdx.x;
-  const int ch = (G + SP_BH_THREADS - 1) / SP_BH_THREADS;
-  const int i0 = min(G, t * ch), i1 = min(G, i0 + ch);
-  double m = INFINITY;
-  for (int i = i0; i < i1; ++i) m = fmin(m, scratch[base + i]);
-  cmin[t] = m;
-  __syncthreads();
-  for (int o = 1; o < SP_BH_THREADS; o <<= 1) {
-    const double other = t + o < SP_BH_THREADS ? cmin[t + o] : INFINITY;
-    __syncthreads();
-    cmin[t] = fmin(cmin[t], other);
-    __syncthreads();
-  }
-  double run = t + 1 < SP_BH_THREADS ? cmin[t + 1] : INFINITY;
-  for (int i = i1 - 1; i >= i0; --i) {
-    run = fmin(run, scratch[base + i]);
-    scratch[base + i] = run;
-  }
-  __threadfence_block();
-  __syncthreads();
-  for (int g = t; g < G; g += SP_BH_THREADS)
-    adj[base + g] = isnan(pvals[base + g]) ? NAN : fmin(1.0, scratch[base + prank[base + g]]);
+  stats::bh_adjust<SP_BH_THREADS, true>(pvals, prank, scratch, adj, base, G, cmin);
 }
 
 __global__ __launch_bounds__(SP_O_THREADS) void sp_summary_kernel(int S, int G, int P, const double* __restrict__ stat,
@@ -559,7 +522,7 @@ __global__ __launch_bounds__(SP_O_THREADS) void sp_summary_kernel(int S, int G, 
   if (P - larger < larger) larger = P - larger;
   const double z = (v - mean) / sqrt(var);
   double pz, l;
-  sp_normal_tail(z, two_tailed, &pz, &l);
+  stats::normal_tail(z, two_tailed, &pz, &l);
   const bool bad = isnan(v);
   count[o] = bad ? -1 : larger;
   pval_sim[o] = bad ? NAN : ((double)larger + 1.0) / ((double)P + 1.0);

@@ -215,6 +215,27 @@ def test_equal_sums_at_the_boundary_go_to_the_higher_gene_index(bleep):
     assert f["heg_genes"][-2:].tolist() == [7, 2]
 
 
+@pytest.mark.parametrize("G,n_top", [(3000, 2500), (5000, 50), (257, 256)])
+def test_top_gene_rank_paths(bleep, G, n_top):
+    """The three paths of the top-n selection under the higher-index tie rule: n_top above the sample of 256 (no threshold,
+    all 3000 genes are candidates, more than the 2048 the LDS ranks: the global rank), many genes behind a threshold, and
+    a sample one short of G.  Two pairs of identical columns, one of them straddling rank n_top."""
+    rng = np.random.default_rng(G)
+    true = rng.random((20, G)) * np.linspace(1.0, 3.0, G)[None, :]
+    by_sum = np.argsort(true.sum(axis=0), kind="stable")
+    lo, hi = sorted((int(by_sum[-n_top]), int(by_sum[-n_top - 1])))     # ranks n_top and n_top + 1 by sum ...
+    true[:, hi] = true[:, lo]                                             # ... now equal: only the higher index is listed
+    a, b = sorted(int(g) for g in by_sum[-3:-1])                          # and a pair well inside the list
+    true[:, b] = true[:, a]
+    pred = true + rng.random((20, G))
+    s, v = true.sum(axis=0), true.var(axis=0)
+    want = np.argsort(s, kind="stable")[-n_top:][::-1]
+    assert want[-1] == hi and lo not in want and abs(int(np.where(want == a)[0][0]) - int(np.where(want == b)[0][0])) == 1
+    f = bleep.score(pred, true, n_top=n_top)
+    assert np.array_equal(f["heg_genes"], want)
+    assert np.array_equal(f["hvg_genes"], np.argsort(v, kind="stable")[-n_top:][::-1])
+
+
 def test_a_segment_in_a_batch_is_bit_identical_to_the_segment_alone(bleep):
     d = ref.scoring_case("nan_gene")
     off = d["offsets"]
